@@ -21,10 +21,16 @@ episode statistics.  `python bench.py --gpus N` with N > 1 STARTS ITS OWN N RANK
 line; when the driver has already started the ranks (WORLD_SIZE / RANK in the environment) this process is one of them.
   --workload cfg2 : 512 envs per GPU (weak scaling; the default and the headline)
   --workload cfg3 : BASELINE configs[2] — 65 536 envs in total, split 65 536/N per rank (strong scaling)
-Whatever the workload, the line also carries `cfg3_strong_scaling`: BASELINE configs[2] (65 536 envs split over the N
-ranks, the multi-GPU configuration north_star names) timed with the same barrier / max-over-ranks protocol right after
-the headline region — so that a `--gpus N` sweep of the default command measures the batch split, not only the
-communication-free weak scaling of 512 envs per GPU.
+
+A plain run times the headline region only.  `--full` adds what takes runs of its own: `cfg3_strong_scaling`
+(BASELINE configs[2], 65 536 envs split over the N ranks, the multi-GPU configuration north_star names, timed with the
+same barrier / max-over-ranks protocol right after the headline region — so that a `--gpus N` sweep measures the batch
+split, not only the communication-free weak scaling of 512 envs per GPU), and on one GPU the CPU baselines and the
+secondary measurements (`extra`; `--no-cpu-baseline` / `--no-extra` leave them out again).
+
+`--dump-outputs DIR` writes what rank 0's last timed launch returned (observations, rewards, dones, self_collision,
+edge_collision) and the env state after it as DIR/<name>.npy in float32; see dump_outputs().  The inputs depend on the
+arguments only (seeded state and action tape), so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -62,12 +68,19 @@ def parse_args(argv=None):
     ap.add_argument('--workload', choices=('cfg2', 'cfg3'), default='cfg2')
     ap.add_argument('--num-envs', type=int, default=None, help='envs per GPU (cfg2: 512) / in total (cfg3: 65536)')
     ap.add_argument('--chunk', type=int, default=None, help='batch-steps per rollout launch (cfg2: 1024)')
-    ap.add_argument('--no-extra', action='store_true', help='skip the secondary measurements')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also time cfg3_strong_scaling and, on one GPU, the CPU baselines and the secondary measurements')
+    ap.add_argument('--no-extra', action='store_true', help='with --full: skip the secondary measurements')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the outputs of the last timed launch as DIR/<name>.npy (float32)")
     ap.add_argument('--dry-run', action='store_true',
                     help='launcher / collective plumbing only: gloo on CPU, the rollout launch replaced by a sleep')
     ap.add_argument('--worker', action='store_true', help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    return args
 
 
 def free_port() -> int:
@@ -202,6 +215,35 @@ def cpu_baseline(num_envs: int, budget_s: float = 5.0):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+
+DUMP_BYTES = 60_000_000  # all files together stay under 64 MB
+
+
+def dump_outputs(path, out, state):
+    """Writes the (T, N, ...) tensors of one rollout launch and the (N, ...) env state after it as float32 .npy files.
+    The per-env-step tensors are flattened to (T * N, ...) rows and share three quarters of DUMP_BYTES, the state gets
+    the rest; a group that does not fit keeps a fixed sample of its rows (numpy default_rng(0), sorted row indices, the
+    same rows in every file of the group), so the files of two runs with the same arguments hold the same elements."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    T, N = out['rewards'].shape
+    steps = {k: v.reshape((T * N,) + tuple(v.shape[2:])) for k, v in out.items() if v is not None}
+    for arrays, budget in ((steps, DUMP_BYTES * 3 // 4), ({'state': state}, DUMP_BYTES // 4)):
+        rows = next(iter(arrays.values())).shape[0]
+        row_bytes = sum(4 * (v.numel() // rows) for v in arrays.values())
+        keep = min(rows, budget // row_bytes)
+        idx = None
+        if keep < rows:
+            idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+            idx = torch.from_numpy(idx).to(state.device)
+        for name, v in arrays.items():
+            if idx is not None:
+                v = v.index_select(0, idx)
+            np.save(os.path.join(path, name + '.npy'), v.to(torch.float32).cpu().numpy())
+
+
 # ------------------------------------------------------------------------------------------------ worker
 
 def worker(args) -> int:
@@ -247,9 +289,10 @@ def worker(args) -> int:
         if not args.dry_run:
             torch.cuda.synchronize()
 
-    def timed_region(N, offset, chunk, K, W):
+    def timed_region(N, offset, chunk, K, W, dump=None):
         """W untimed + exactly K timed rollout launches of (chunk, N) bracketed by barrier + synchronize on both sides;
-        returns (max-over-ranks seconds, env-steps of all ranks, HIP-event average launch seconds on this rank, blocks)"""
+        returns (max-over-ranks seconds, env-steps of all ranks, HIP-event average launch seconds on this rank, blocks).
+        `dump`: a directory for dump_outputs() of the last timed launch, written after the timed region."""
         blocks = min(W + K, MAX_TAPE_BLOCKS)
         if args.dry_run:
             env, tape = None, None
@@ -277,8 +320,9 @@ def worker(args) -> int:
         t0 = time.perf_counter()
         if ev:
             ev[0].record()
-        for i in range(W, W + K):
+        for i in range(W, W + K - 1):
             launch(i)
+        last = launch(W + K - 1)   # (kept for --dump-outputs; the earlier launches' outputs are freed on return as before)
         if ev:
             ev[1].record()
         sync()
@@ -290,26 +334,31 @@ def worker(args) -> int:
             dist.all_reduce(t[:1], op=dist.ReduceOp.MAX)
             dist.all_reduce(t[1:], op=dist.ReduceOp.SUM)
         avg = ev[0].elapsed_time(ev[1]) * 1e-3 / K if ev else float(t[0].item()) / K
-        del env, tape
+        if dump is not None and last is not None:
+            dump_outputs(dump, last, env.envs)
+        del env, tape, last
         return float(t[0].item()), float(t[1].item()), avg, blocks
 
-    elapsed, total_env_steps, avg_launch_s, blocks = timed_region(N, offset, chunk, K, W)
-
-    # BASELINE configs[2] split over the ranks, same protocol (see the module docstring)
-    g3 = 65536
-    off3, n3 = shard_range(g3, rank, n_gpus)
-    chunk3 = 64 if n3 > 16384 else 128
-    k3, w3 = (K, W) if args.workload == 'cfg3' else (min(K, 20), 3)
-    if args.workload == 'cfg3' and (args.num_envs in (None, g3)) and args.chunk in (None, chunk3):
-        el3, tot3, avg3 = elapsed, total_env_steps, avg_launch_s
-    else:
-        el3, tot3, avg3, _ = timed_region(n3, off3, chunk3, k3, w3)
+    elapsed, total_env_steps, avg_launch_s, blocks = timed_region(
+        N, offset, chunk, K, W, dump=args.dump_outputs if rank == 0 else None)
 
     # every rank's own record: the first run on a multi-GPU node should explain itself
     mine = {'rank': rank, 'local_rank': local_rank, 'device': None if args.dry_run else torch.cuda.get_device_name(local_rank),
-            'env_offset': int(offset), 'num_envs': int(N), 'cfg3_shard': [int(off3), int(off3 + n3)],
+            'env_offset': int(offset), 'num_envs': int(N),
             'comm_init_s': round(t_init, 3), 'avg_launch_ms': round(avg_launch_s * 1e3, 4),
-            'cfg3_avg_launch_ms': round(avg3 * 1e3, 4), 'host': os.uname().nodename, 'pid': os.getpid()}
+            'host': os.uname().nodename, 'pid': os.getpid()}
+
+    if args.full:
+        # BASELINE configs[2] split over the ranks, same protocol (see the module docstring)
+        g3 = 65536
+        off3, n3 = shard_range(g3, rank, n_gpus)
+        chunk3 = 64 if n3 > 16384 else 128
+        k3, w3 = (K, W) if args.workload == 'cfg3' else (min(K, 20), 3)
+        if args.workload == 'cfg3' and (args.num_envs in (None, g3)) and args.chunk in (None, chunk3):
+            el3, tot3, avg3 = elapsed, total_env_steps, avg_launch_s
+        else:
+            el3, tot3, avg3, _ = timed_region(n3, off3, chunk3, k3, w3)
+        mine.update({'cfg3_shard': [int(off3), int(off3 + n3)], 'cfg3_avg_launch_ms': round(avg3 * 1e3, 4)})
     ranks = [mine]
     if distributed:
         ranks = [None] * world
@@ -361,23 +410,24 @@ def worker(args) -> int:
                          'limiter': 'observation stores (HBM)' if lane else 'instruction issue of one wave per env',
                          'note': '`achieved` = SURVEY 8(d) bytes of an UNFUSED step/reset pair; `traffic` / `frac_real` = '
                                  'rocprofv3 counter bytes of this launch shape (profiles/hbm_traffic.json)'},
-            'cfg3_strong_scaling': {
+        }
+        if args.full:
+            line['cfg3_strong_scaling'] = {
                 'value': tot3 / el3, 'unit': 'env-steps/s', 'scaling': 'strong', 'global_num_envs': g3,
                 'num_envs_per_gpu': n3, 'batch_steps_per_launch': chunk3, 'steps': k3, 'warmup': w3,
                 'ms_per_step': el3 / k3 * 1e3, 'avg_launch_ms': avg3 * 1e3,
                 'obs_and_outputs_GBs_this_rank': (4 * OBS_ELEMS + 23) * n3 * chunk3 / avg3 / 1e9,
-                'what': 'BASELINE configs[2] split over the ranks, same protocol as the headline'},
-        }
+                'what': 'BASELINE configs[2] split over the ranks, same protocol as the headline'}
         line['ranks'] = ranks
         if args.dry_run:
             line['dry_run'] = True
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             try:
                 line['cpu_baseline'] = cpu_baseline(512,
                                                     budget_s=0.5 if args.dry_run else 5.0)
             except Exception as e:  # the baseline is a reported extra: never lose the bench line over it
                 line['cpu_baseline'] = {'error': repr(e)}
-        if n_gpus == 1 and not args.no_extra and not args.dry_run:
+        if args.full and n_gpus == 1 and not args.no_extra and not args.dry_run:
             line['extra'] = extra_measurements(device)
             for k, what in DESCRIPTIONS.items():   # what each extra measures: stderr (and profiles/bench_keys.md), not the line
                 print(f'# {k}: {what}', file=sys.stderr)
@@ -848,9 +898,10 @@ def key_numbers(line):
     def g(k, f='value'):
         v = ex.get(k, {}).get(f)
         return None if v is None else (float('%.4g' % v) if isinstance(v, float) else v)
+    c3 = line.get('cfg3_strong_scaling')   # (--full only, like `extra`)
     return {
         'cfg2_rollout_eps': float('%.4g' % line['value']),
-        'cfg3_strong_scaling_eps': float('%.4g' % line['cfg3_strong_scaling']['value']),
+        'cfg3_strong_scaling_eps': None if c3 is None else float('%.4g' % c3['value']),
         'cfg3_rollout_eps': g('rollout_cfg3_65536'), 'cfg3_rollout_ms': g('rollout_cfg3_65536', 'ms'),
         'cfg3_rollout_frac_real': g('rollout_cfg3_65536', 'frac_real'),
         'cfg3_share_8192_eps': g('rollout_8192'),

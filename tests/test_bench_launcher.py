@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -23,7 +25,7 @@ def _run(*flags, env=None):
 
 
 def test_gpus_2_spawns_two_ranks():
-    d = _run('--gpus', '2', '--dry-run', '--steps', '3', '--warmup', '1')
+    d = _run('--gpus', '2', '--dry-run', '--full', '--steps', '3', '--warmup', '1')
     assert d['n_gpus'] == 2 and d['config']['world_size'] == 2 and d['config']['backend'] == 'gloo'
     assert d['steps'] == 3 and d['warmup'] == 1 and d['scaling'] == 'weak'
     # whole-job value: both ranks' env-steps over the max-over-ranks time
@@ -37,14 +39,14 @@ def test_gpus_2_spawns_two_ranks():
 
 
 def test_cfg3_is_split_over_the_ranks():
-    d = _run('--gpus', '2', '--dry-run', '--steps', '2', '--warmup', '0', '--workload', 'cfg3')
+    d = _run('--gpus', '2', '--dry-run', '--full', '--steps', '2', '--warmup', '0', '--workload', 'cfg3')
     assert d['config']['global_num_envs'] == 65536 and d['config']['num_envs_per_gpu'] == 32768
     assert d['scaling'] == 'strong' and d['config']['baseline_config'] == 'BASELINE.json configs[2]'
     assert abs(d['cfg3_strong_scaling']['value'] - d['value']) / d['value'] < 1e-9   # the same region, not timed twice
 
 
 def test_single_process_default_and_cpu_baseline_legs():
-    d = _run('--dry-run', '--steps', '2', '--warmup', '1')
+    d = _run('--dry-run', '--full', '--steps', '2', '--warmup', '1')
     assert d['n_gpus'] == 1 and d['config']['world_size'] == 1
     assert str(d['config']['batch_steps_per_launch']) in d['config']['workload']
     cb = d['cpu_baseline']
@@ -69,7 +71,8 @@ def test_worker_under_an_external_torchrun():
 def test_world_size_8_with_an_uneven_global_batch():
     """the 8-GPU shape north_star names, on gloo: 65 537 envs do not divide by 8 — every rank gets a contiguous block,
     the blocks tile the batch, the line's key numbers carry the strong-scaling value"""
-    d = _run('--gpus', '8', '--dry-run', '--steps', '2', '--warmup', '0', '--workload', 'cfg3', '--num-envs', '65537')
+    d = _run('--gpus', '8', '--dry-run', '--full', '--steps', '2', '--warmup', '0', '--workload', 'cfg3',
+             '--num-envs', '65537')
     assert d['n_gpus'] == 8 and d['config']['world_size'] == 8 and d['scaling'] == 'strong'
     assert d['config']['global_num_envs'] == 65537
     assert d['config']['num_envs_per_gpu'] == 8193            # rank 0's block: the remainder goes to the first ranks
@@ -84,3 +87,60 @@ def test_world_size_8_with_an_uneven_global_batch():
     assert [r['rank'] for r in ranks] == list(range(8))
     assert [(r['env_offset'], r['num_envs']) for r in ranks] == blocks
     assert all(r['comm_init_s'] >= 0 and r['avg_launch_ms'] > 0 for r in ranks)
+
+
+def test_plain_run_times_the_headline_only():
+    """without --full the line carries the headline region and nothing that takes runs of its own"""
+    d = _run('--dry-run', '--steps', '3', '--warmup', '1')
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0
+    assert d['metric'] == 'env_steps_per_s' and d['unit'] == 'env-steps/s' and d['higher_is_better'] is True
+    assert d['dtype'] == 'i32'
+    assert 'cfg3_strong_scaling' not in d and 'cpu_baseline' not in d and 'extra' not in d
+    assert d['key']['cfg3_strong_scaling_eps'] is None
+
+
+def test_dump_outputs_keeps_a_fixed_sample_within_the_budget(tmp_path, monkeypatch):
+    """dump_outputs() on host tensors of a rollout's shapes: float32 files, the byte budget, the same sample twice"""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 300_000)
+    T, N = 40, 64
+    g = torch.Generator().manual_seed(0)
+    out = {'observations': torch.rand((T, N, 3, 5, 5), generator=g), 'rewards': torch.rand((T, N), generator=g),
+           'dones': torch.rand((T, N), generator=g) < 0.5, 'self_collision': torch.zeros((T, N), dtype=torch.bool),
+           'edge_collision': torch.ones((T, N), dtype=torch.bool)}
+    state = torch.rand((N, 3, 9, 9), generator=g)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), out, state)
+    files = sorted(p.name for p in (tmp_path / 'a').iterdir())
+    assert files == ['dones.npy', 'edge_collision.npy', 'observations.npy', 'rewards.npy', 'self_collision.npy',
+                     'state.npy']
+    assert sum(p.stat().st_size for p in (tmp_path / 'a').iterdir()) <= 300_000 + 6 * 128
+    a = {f[:-4]: np.load(tmp_path / 'a' / f) for f in files}
+    for f in files:
+        assert a[f[:-4]].dtype == np.float32
+        assert np.array_equal(a[f[:-4]], np.load(tmp_path / 'b' / f))
+    rows = a['rewards'].shape[0]
+    assert 0 < rows < T * N and a['observations'].shape == (rows, 3, 5, 5)
+    # the sampled rows are the same rows in every per-step file
+    flat_r, flat_o = out['rewards'].reshape(-1).numpy(), out['observations'].reshape(T * N, -1).numpy()
+    idx = np.flatnonzero(np.isin(flat_r, a['rewards']))
+    assert len(idx) == rows and np.array_equal(flat_o[idx], a['observations'].reshape(rows, -1))
+    assert a['state'].shape == (N, 3, 9, 9) and np.array_equal(a['state'], state.numpy())  # (fits: kept whole)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_on_the_gpu_are_identical_from_run_to_run(tmp_path):
+    """two runs with the same arguments dump the same arrays (the inputs are seeded), under 64 MB in all"""
+    import numpy as np
+    for d in ('a', 'b'):
+        line = _run('--steps', '2', '--warmup', '1', '--dump-outputs', str(tmp_path / d))
+        assert line['steps'] == 2 and 'extra' not in line
+    files = sorted(p.name for p in (tmp_path / 'a').iterdir())
+    assert 'observations.npy' in files and 'rewards.npy' in files and 'state.npy' in files
+    assert sum(p.stat().st_size for p in (tmp_path / 'a').iterdir()) < 64 * 10**6
+    for f in files:
+        x, y = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert x.dtype == np.float32 and np.array_equal(x, y), f
+    assert np.load(tmp_path / 'a' / 'state.npy').shape == (512, 3, 9, 9)

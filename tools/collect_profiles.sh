@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # 1. the bench line (un-profiled), exactly as the driver runs it, and with the defaults
-python3 $R/bench.py > $OUT/${TAG}_bench_cfg2.json 2> $OUT/bench.err
+python3 $R/bench.py --full > $OUT/${TAG}_bench_cfg2.json 2> $OUT/bench.err
 python3 $R/bench.py --steps 20 --warmup 5 --no-extra --no-cpu-baseline > $OUT/${TAG}_bench_cfg2_steps20.json 2>> $OUT/bench.err
 # 2. kernel trace + stats of the same command
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o $TAG -- python3 $R/bench.py --no-extra --no-cpu-baseline > $OUT/${TAG}_cfg2_rollout_bench_under_rocprof.json 2> $OUT/trace.err

@@ -264,12 +264,27 @@ int wurm_grid_step_slot(wurm_single_call *c, const wurm_single_slabs *slabs, int
  * status (N) uint8: 0 = rolled out; 1 = the env's state is outside the kernel's domain (not a well-formed snake):
  * it is left untouched and its outputs are not written.  Step t uses call0 + 2t (env step and the sampling draw),
  * its reset call0 + 2t + 1.  Arithmetic order of the policy: see wurm_amd/csrc/policy_rollout.hpp.
- * Supported: 9 <= size <= 11, 0 <= obs_n <= 3. */
+ * Supported: 9 <= size <= 64, 0 <= obs_n <= 6 (sizes 9-11 with obs_n <= 3 on policy_rollout.hpp's kernels, the rest on
+ * policy_wide.hpp's; WURM_POLICY_WIDE = 1 sends every shape to the latter).  Outside: WURM_ERR_UNSUPPORTED. */
 int wurm_single_policy_rollout(float *envs, const float *obs0, const float *params, int64_t *actions, float *probs,
                                float *values, float *reward, uint8_t *done, uint8_t *self_collision,
                                uint8_t *edge_collision, float *obs, uint8_t *status, int obs_n, int64_t num_envs,
                                int size, int64_t num_steps, uint64_t seed, uint64_t call0, int64_t env_offset,
                                void *stream);
+
+/* wurm_single_policy_rollout with the observation mode as an argument: WURM_OBS_PARTIAL (obs_n as there) or
+ * WURM_OBS_POSITIONS (E = 4: head row, head column, food row, food column; obs_n ignored), 9 <= size <= 64.  The image
+ * modes and WURM_OBS_NONE return WURM_ERR_UNSUPPORTED: the reference's feed-forward agent takes a flat observation
+ * (experiments/main.py:129-137). */
+int wurm_single_policy_rollout_mode(float *envs, const float *obs0, const float *params, int64_t *actions, float *probs,
+                                    float *values, float *reward, uint8_t *done, uint8_t *self_collision,
+                                    uint8_t *edge_collision, float *obs, uint8_t *status, int obs_mode, int obs_n,
+                                    int64_t num_envs, int size, int64_t num_steps, uint64_t seed, uint64_t call0,
+                                    int64_t env_offset, void *stream);
+
+/* Name of the kernel that served the calling thread's last policy rollout: "policy_s9", "policy_generic" (both
+ * policy_rollout.hpp), "policy_wide" (policy_wide.hpp), or "none". */
+const char *wurm_policy_last_route(void);
 
 /* wurm.utils.env_consistency / snake_consistency (wurm/utils.py:113-178) as a per-env error bitmask
  * (bit i = i-th check failed, WURM_CHK_*; 0 = consistent).  err out (N) uint32. */
@@ -303,6 +318,14 @@ int wurm_grid_rollout(float *envs, const void *actions, int actions_dtype, float
                       uint8_t *edge_collision, float *obs, int obs_mode, int obs_n, int64_t num_envs, int size,
                       int64_t num_steps, int start_y, int start_x, uint64_t seed, uint64_t call0,
                       int64_t env_offset, const int32_t *inject_food, const int32_t *inject_reset, void *stream);
+
+/* The fused acting loop of wurm_single_policy_rollout for SimpleGridworld, 'positions' observations (E = 4), start
+ * location as wurm_grid_rollout's, 5 <= size <= 64.  Same outputs minus self_collision.  status (N): 1 = the env does not
+ * hold exactly one agent and one food (left untouched, its outputs not written). */
+int wurm_grid_policy_rollout(float *envs, const float *obs0, const float *params, int64_t *actions, float *probs,
+                             float *values, float *reward, uint8_t *done, uint8_t *edge_collision, float *obs,
+                             uint8_t *status, int64_t num_envs, int size, int64_t num_steps, int start_y, int start_x,
+                             uint64_t seed, uint64_t call0, int64_t env_offset, void *stream);
 
 /* wurm_grid_rollout (RNG mode) for a caller that keeps SimpleGridworld's mirror (wurm_grid_resident_bytes; *resident_valid and
  * resident_lazy as the fields of wurm_single_call): where the one-env-per-lane kernel serves the launch, the state comes from

@@ -28,6 +28,7 @@ SYMBOLS = [
     'wurm_multi_rollout', 'wurm_multi_rollout_resident',
     'wurm_multi_colours', 'wurm_orientations',
     'wurm_a2c_returns', 'wurm_a2c_returns_backward', 'wurm_single_stats', 'wurm_single_policy_rollout',
+    'wurm_single_policy_rollout_mode', 'wurm_grid_policy_rollout', 'wurm_policy_last_route',
 ]
 
 

@@ -23,6 +23,7 @@ struct Options {
     long long multi_shape_kernels;   // WURM_MULTI_SHAPE_KERNELS   MultiSnake: kernels with K, S and the crop radius compiled in for the reference's experiment shapes (1; 0 = the generic kernels)
     long long gridworld_lane_epw;    // WURM_GRIDWORLD_LANE_EPW    SimpleGridworld lane rollout, image modes: envs per wave (4..64; -1 = by batch size)
     long long grid_rollout_min_size; // WURM_GRID_ROLLOUT_MIN_SIZE SingleSnake rollouts on LDS clock grids from this grid size on (-1 = by observation mode: 14 / 18 / 26; 12 = every size they serve)
+    long long policy_wide;           // WURM_POLICY_WIDE           1 = fused actor on policy_wide_kernel even where policy_rollout.hpp's kernels serve (S <= 11, n <= 3)
 };
 
 extern Options opt;

@@ -20,6 +20,8 @@
 //
 // Domain: SingleSnake, grids of at most 128 cells (S <= 11), partial_n crop with n <= 3, envs in a well-formed state
 // (fast_init: what reset / step+reset produce).  An env outside the domain is left untouched and flagged in `status`.
+// Every other configuration of the reference's feed-forward experiment (SingleSnake 9 <= S <= 64 with partial_n, n <= 6,
+// or positions; SimpleGridworld positions) runs policy_wide.hpp's kernel, with the same arithmetic.
 #pragma once
 #include <cstdlib>
 
@@ -446,6 +448,7 @@ void policy_rollout_s9_kernel(PolicyArgs p)
     }
 }
 
+#ifndef WURM_SINGLE_SNAKE_DEVICE_CODE_ONLY // (policy_wide.hip includes this file for the pieces above only)
 static int launch_policy_rollout(const PolicyArgs &p, int obs_n, void *stream)
 {
     const int W2 = (2 * obs_n + 1) * (2 * obs_n + 1), EP = (3 * W2 + 3) & ~3;
@@ -475,5 +478,6 @@ static int launch_policy_rollout(const PolicyArgs &p, int obs_n, void *stream)
     }
     return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
 }
+#endif
 
 } // namespace wurm

@@ -1,0 +1,273 @@
+// policy_wide.hpp — the fused acting loop of policy_rollout.hpp for every configuration the reference's feed-forward
+// experiment accepts (experiments/main.py:129-137: FeedforwardAgent(num_inputs = 4) for 'positions', 3 (2n+1)^2 for
+// 'partial_n'):
+//   SingleSnake      9 <= S <= 64, partial_n with 0 <= n <= 6 (E = 3 (2n+1)^2 <= 507) or positions (E = 4);
+//   SimpleGridworld  5 <= S <= 64, positions (E = 4), the fixed start location.
+// Included by policy_wide.hip after single_snake.hip (device code only) and policy_rollout.hpp (PolicyArgs, exp_spec,
+// tree_sum5); not a standalone header.
+//
+// The loop is rollout_generic's (one env per wave, Env<CPL> at every cells-per-lane bucket, the scalar carry of `Fast`
+// for snakes) with the action tape replaced by the policy: per step, probs / value / sampled action from the observation
+// in the wave's LDS input buffer, then step, observation to HBM and to that buffer, reset on done.  The arithmetic is
+// policy_rollout.hpp's spec (two interleaved fmaf chains per hidden unit, tree_sum5 heads, exp_spec softmax, inverse-CDF
+// sampling with the RNG_POLICY draw of call0 + 2t), so the results are bit-identical to oracle/policy.c and, on the
+// shapes both kernels serve, to policy_rollout_kernel / policy_rollout_s9_kernel.
+//
+// First-layer weights: W1 is 64 E floats (130 KB at E = 507), too many for registers beyond n = 3.  The workgroup
+// copies it ONCE into LDS, shared by its waves, as (input pair, unit) float2s: lane j reads the pair of inputs
+// (2i, 2i+1) of unit j at float2 index 64 i + j, so one ds_read_b64 per wave moves 32 consecutive lanes x 8 bytes =
+// all 64 banks, conflict-free.  The input vector is read as broadcast ds_read_b128s.  Inputs are zero-padded to a
+// multiple of 16 (weights and inputs both 0): fmaf(0, 0, acc) == acc except that -0 becomes +0, which the ReLU after
+// the layer maps to the same +0.  W2 (64 x 64) stays in registers as in policy_rollout.hpp.
+// LDS per workgroup = 256 EP + wpb (4 EP + 256 + S^2 rounded to 16) bytes (EP = E rounded up to 16; the S^2 bytes are
+// write_obs's class map for crops on grids of more than 128 cells); wpb = waves per workgroup, as many as fit in 160 KiB
+// (at most 8), fewer for small batches so that the workgroups still spread over the CUs.
+#pragma once
+
+namespace wurm {
+
+struct PolicyWideArgs {
+    PolicyArgs p;        // selfc == nullptr for SimpleGridworld
+    int E, EP;           // observation size, and rounded up to 16
+    int obs_mode, obs_n; // WURM_OBS_PARTIAL (SingleSnake) or WURM_OBS_POSITIONS
+    int start_y, start_x;
+    int wpb, wave_bytes; // waves per workgroup, LDS bytes per wave
+};
+
+// the policy of one wave with the first layer in LDS (lane j = hidden unit j of both layers, column j of the heads)
+struct PolicyWide {
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    f2 w2[32];
+    float wp0, wp1, wp2, wp3, wv, bias1, bias2, bp0, bp1, bp2, bp3, bv0;
+    const f2 *w1;   // LDS: (EP / 2, 64) pairs, shared by the workgroup
+    float *x, *h1;  // LDS of this wave: x[EP] (input, zero padded), h1[64]
+    int EP;
+
+    __device__ __forceinline__ void load(const float *params, int E, int ep, int lane, const f2 *w1_lds, float *x_lds)
+    {
+        const float *b1 = params + (long long)64 * E, *W2p = b1 + 64, *b2 = W2p + 64 * 64, *Wp = b2 + 64,
+                    *bp = Wp + 4 * 64, *Wv = bp + 4, *bv = Wv + 64;
+#pragma unroll
+        for (int k = 0; k < 32; ++k) {
+            w2[k].x = W2p[lane * 64 + 2 * k];
+            w2[k].y = W2p[lane * 64 + 2 * k + 1];
+        }
+        wp0 = Wp[lane]; wp1 = Wp[64 + lane]; wp2 = Wp[128 + lane]; wp3 = Wp[192 + lane]; wv = Wv[lane];
+        bias1 = b1[lane]; bias2 = b2[lane];
+        bp0 = bp[0]; bp1 = bp[1]; bp2 = bp[2]; bp3 = bp[3]; bv0 = bv[0];
+        w1 = w1_lds;
+        x = x_lds;
+        h1 = x_lds + ep;
+        EP = ep;
+    }
+
+    // probs, value = model(x in LDS), action = Categorical(probs).sample() with the uniform u; all results wave-uniform
+    __device__ __forceinline__ int act(int lane, float u, float &p0, float &p1, float &p2, float &p3, float &value) const
+    {
+        wave_lds_sync();
+        f2 acc2 = {bias1, 0.0f};
+        const f2 *wl = w1 + lane;
+        // 16 inputs per batch: 4 broadcast ds_read_b128 of x and 8 ds_read_b64 of weights in flight, then 8 v_pk_fma
+#pragma unroll 2
+        for (int k0 = 0; k0 < EP; k0 += 16) {
+            float4 xs[4];
+            f2 ws[8];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) xs[i] = *(const float4 *)(x + k0 + 4 * i);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) ws[i] = wl[(k0 / 2 + i) * 64];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const f2 lo = {xs[i].x, xs[i].y}, hi = {xs[i].z, xs[i].w};
+                acc2 = __builtin_elementwise_fma(ws[2 * i], lo, acc2);
+                acc2 = __builtin_elementwise_fma(ws[2 * i + 1], hi, acc2);
+            }
+        }
+        float acc = acc2.x + acc2.y;
+        h1[lane] = acc > 0.0f ? acc : 0.0f;
+        wave_lds_sync();
+        acc2.x = bias2;
+        acc2.y = 0.0f;
+#pragma unroll
+        for (int k0 = 0; k0 < 16; k0 += 8) {
+            float4 hs[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) hs[k] = *(const float4 *)(h1 + 4 * (k0 + k));
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const f2 lo = {hs[k].x, hs[k].y}, hi = {hs[k].z, hs[k].w};
+                acc2 = __builtin_elementwise_fma(w2[2 * (k0 + k)], lo, acc2);
+                acc2 = __builtin_elementwise_fma(w2[2 * (k0 + k) + 1], hi, acc2);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        acc = acc2.x + acc2.y;
+        const float h2 = acc > 0.0f ? acc : 0.0f;
+        float t0 = wp0 * h2, t1 = wp1 * h2, t2 = wp2 * h2, t3 = wp3 * h2, t4 = wv * h2;
+        tree_sum5(t0, t1, t2, t3, t4);
+        const float l0 = t0 + bp0, l1 = t1 + bp1, l2 = t2 + bp2, l3 = t3 + bp3;
+        value = t4 + bv0;
+        const float m = fmaxf(fmaxf(l0, l1), fmaxf(l2, l3));
+        const float e0 = exp_spec(l0 - m), e1 = exp_spec(l1 - m), e2 = exp_spec(l2 - m), e3 = exp_spec(l3 - m);
+        const float rs = 1.0f / (((e0 + e1) + e2) + e3);
+        p0 = e0 * rs; p1 = e1 * rs; p2 = e2 * rs; p3 = e3 * rs;
+        const float c0 = p0, c1 = c0 + p1, c2 = c1 + p2;
+        return uniform((u >= c0 ? 1 : 0) + (u >= c1 ? 1 : 0) + (u >= c2 ? 1 : 0));
+    }
+};
+
+// 'positions' of a snake from the carried scalars: (head row, head column, food row, food column), 0 for a missing
+// head / food — write_obs's argmax of the two channels, which for fast_init's at most one food is the food cell itself
+__device__ __forceinline__ void fast_positions(const Geo &g, const Fast &f, float *__restrict__ o, float *lds_copy)
+{
+    const int h = f.hc < 0 ? 0 : f.hc, fc = f.food < 0 ? 0 : f.food;
+    const int hy = div_size(h, g.rcpS), fy = div_size(fc, g.rcpS), lane = g.lane;
+    const float v = (float)(lane == 0 ? hy : lane == 1 ? h - hy * g.S : lane == 2 ? fy : fc - fy * g.S);
+    if (lane < 4) {
+        o[lane] = v;
+        lds_copy[lane] = v;
+    }
+}
+
+// at most 8 waves per workgroup; 4 from 48 cells per lane on, where the snake's body registers and W2 need more than the
+// 256 VGPRs an 8-wave workgroup leaves a lane (scratch otherwise)
+template <int CPL>
+constexpr int policy_wide_max_wpb() { return CPL >= 48 ? 4 : 8; }
+
+template <int CPL, bool SNAKE>
+__global__ __launch_bounds__(64 * policy_wide_max_wpb<CPL>()) void policy_wide_kernel(PolicyWideArgs a)
+{
+    typedef PolicyWide::f2 f2;
+    const PolicyArgs &p = a.p;
+    const int E = a.E, EP = a.EP;
+    {   // W1 (64, E) -> LDS as (EP / 2, 64) pairs, zero padded: input k of unit j at float 128 (k / 2) + 2 j + (k & 1).
+        // Coalesced reads of W1 in its own order, scattered LDS writes.
+        float *w1f = (float *)wurm_lds;
+        const int n = 64 * E, pad = EP - E;
+#pragma unroll 4
+        for (int i = (int)threadIdx.x; i < n; i += (int)blockDim.x) {
+            const int j = i / E, k = i - j * E;
+            w1f[(k >> 1) * 128 + 2 * j + (k & 1)] = p.params[i];
+        }
+        for (int i = (int)threadIdx.x; i < 64 * pad; i += (int)blockDim.x) {
+            const int j = i / pad, k = E + (i - j * pad);
+            w1f[(k >> 1) * 128 + 2 * j + (k & 1)] = 0.0f;
+        }
+    }
+    __syncthreads();
+    const int wave = uniform((int)(threadIdx.x >> 6));
+    const long long env = xcd_block(blockIdx.x, gridDim.x) * a.wpb + wave;
+    if (env >= p.N) return;
+    signed char *wl = wurm_lds + (size_t)EP * 256 + (size_t)wave * a.wave_bytes;
+    float *x = (float *)wl;
+    signed char *cls = wl + (size_t)EP * 4 + 256; // write_obs's class map (crops of grids > 128 cells)
+    const Geo g = make_geo<CPL>(p.S);
+    const int lane = g.lane;
+    float *envp = p.envs + env * (SNAKE ? 3 : 2) * g.C;
+    Env<CPL> e;
+    load_state<CPL, SNAKE>(envp, g, e);
+    Fast f = {-1, 0, 0, 0, 0, -1};
+    bool ok;
+    if constexpr (SNAKE) {
+        ok = fast_init<CPL>(e, g, f);
+    } else { // exactly one agent and one food
+        const int counts = wave_sum_i32(__popcll(e.head) | (__popcll(e.food) << 16));
+        ok = counts == (1 | (1 << 16));
+    }
+    if (!uniform((int)ok)) {
+        if (lane == 0) p.status[env] = 1;
+        return;
+    }
+    if (lane == 0) p.status[env] = 0;
+    PolicyWide pol;
+    pol.load(p.params, E, EP, lane, (const f2 *)wurm_lds, x);
+    for (int k = lane; k < EP; k += 64) x[k] = k < E ? p.obs0[env * E + k] : 0.0f;
+
+    const u64 env_id = (u64)(p.env_offset + env);
+    const bool positions = a.obs_mode == WURM_OBS_POSITIONS;
+    const bool small_crop = SNAKE && CPL <= 2 && !positions;
+    const Crop cg = make_crop(lane, small_crop ? a.obs_n : 0);
+    const long long obs_stride = p.N * E;
+    float *obs_t = p.obs + env * E;
+    u64 call = p.call;
+    for (long long t0 = 0; t0 < p.T; t0 += 64) {
+        const int nt = (int)min((long long)64, p.T - t0);
+        const long long my_t = t0 + lane;
+        const float my_u = u01(rng_words(p.seed, p.call + 2ull * (u64)my_t, env_id, RNG_POLICY, 0).w[0]);
+        int my_act = 0, my_flags = 0; // flags: done | self collision << 1 | edge collision << 2 | ate << 3
+        float my_val = 0.0f, my_p0 = 0.0f, my_p1 = 0.0f, my_p2 = 0.0f, my_p3 = 0.0f;
+        for (int j = 0; j < nt; ++j, obs_t += obs_stride, call += 2) {
+            float p0, p1, p2, p3, value;
+            const int act = pol.act(lane, __int_as_float(lane_value(__float_as_int(my_u), j)), p0, p1, p2, p3, value);
+            StepOut out;
+            if constexpr (SNAKE) { // env.step(action) (single_snake.py:197-304), observation to HBM and LDS, env.reset(done)
+                fast_step<CPL>(e, g, f, act, act, out, p.seed, call, env_id, false, -1);
+                if (positions) {
+                    fast_positions(g, f, obs_t, x);
+                } else if (small_crop) {
+                    if constexpr (CPL <= 2) fast_partial_small<CPL>(e, g, f, obs_t, cg, x);
+                } else {
+                    fast_sync_bits<CPL>(e, g, f);
+                    write_obs<CPL, true>(e, g, f.hc, obs_t, WURM_OBS_PARTIAL, a.obs_n, cls, x);
+                }
+                if (out.done) fast_reset<CPL>(e, g, f, p.seed, call + 1ull, env_id, nullptr);
+            } else {               // simple_gridworld.py:135-202, :111-133, :225-268
+                step_core<CPL, false, false>(e, g, nullptr, (long long)act, out, p.seed, call, env_id, false, -1, cls);
+                write_obs<CPL, false>(e, g, out.headcell, obs_t, WURM_OBS_POSITIONS, 0, cls, x);
+                if (out.done) reset_core<CPL, false>(e, g, p.seed, call + 1ull, env_id, nullptr, a.start_y, a.start_x);
+            }
+            if (lane == j) {
+                my_act = (int)out.action;
+                my_flags = out.done | (out.selfc << 1) | (out.edgec << 2) | (out.reward != 0.0f ? 8 : 0);
+                my_val = value; my_p0 = p0; my_p1 = p1; my_p2 = p2; my_p3 = p3;
+            }
+        }
+        if (lane < nt) {
+            const long long i = my_t * p.N + env;
+            p.actions[i] = (long long)my_act;
+            p.values[i] = my_val;
+            *(float4 *)(p.probs + 4 * i) = make_float4(my_p0, my_p1, my_p2, my_p3);
+            p.reward[i] = (my_flags & 8) ? 1.0f : 0.0f;
+            p.done[i] = (uint8_t)(my_flags & 1);
+            if (SNAKE) p.selfc[i] = (uint8_t)((my_flags >> 1) & 1);
+            p.edgec[i] = (uint8_t)((my_flags >> 2) & 1);
+        }
+    }
+    if constexpr (SNAKE) fast_sync_bits<CPL>(e, g, f);
+    store_state<CPL, SNAKE>(envp, g, e);
+}
+
+template <bool SNAKE>
+static int launch_policy_wide_cpl(PolicyWideArgs a, int cpl, hipStream_t st)
+{
+    constexpr int LDS_MAX = 160 * 1024, W1_LDS_PER_INPUT = 64 * 4;
+    const int S = a.p.S;
+    a.EP = (a.E + 15) & ~15;
+    a.wave_bytes = a.EP * 4 + 64 * 4 + ((S * S + 15) & ~15);
+    const int fit = (LDS_MAX - a.EP * W1_LDS_PER_INPUT) / a.wave_bytes;
+    // as many waves per workgroup as fit (each workgroup copies W1 once), but no fewer workgroups than CUs
+    const long long per_cu = (a.p.N + 255) / 256, most = cpl >= 48 ? 4 : 8;
+    a.wpb = (int)std::max(1ll, std::min({(long long)fit, most, per_cu}));
+    const size_t lds = (size_t)a.EP * W1_LDS_PER_INPUT + (size_t)a.wpb * a.wave_bytes;
+    dim3 block(64 * a.wpb), grid((unsigned)((a.p.N + a.wpb - 1) / a.wpb));
+    auto go = [&](auto kernel) {
+        if (lds > 65536) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        WURM_LAUNCH(kernel, grid, block, lds, st, a);
+    };
+    (void)hipGetLastError();
+    switch (cpl) {
+    case 2: go(policy_wide_kernel<2, SNAKE>); break;
+    case 4: go(policy_wide_kernel<4, SNAKE>); break;
+    case 8: go(policy_wide_kernel<8, SNAKE>); break;
+    case 16: go(policy_wide_kernel<16, SNAKE>); break;
+    case 24: go(policy_wide_kernel<24, SNAKE>); break;
+    case 32: go(policy_wide_kernel<32, SNAKE>); break;
+    case 48: go(policy_wide_kernel<48, SNAKE>); break;
+    case 64: go(policy_wide_kernel<64, SNAKE>); break;
+    default: return WURM_ERR_UNSUPPORTED;
+    }
+    return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+}
+
+} // namespace wurm

@@ -486,10 +486,11 @@ __device__ __forceinline__ int cell_class(const Env<CPL> &e, const Geo &g, int k
 }
 
 // _observe of one env (single_snake.py:130-195, simple_gridworld.py:111-133) from registers.
-// headcell: the env's head cell (-1 = none).
+// headcell: the env's head cell (-1 = none).  lds_copy (partial_n and positions only): a second target for the same
+// observation, for a consumer inside the kernel (policy_wide.hpp); off by default.
 template <int CPL, bool SNAKE>
 __device__ __forceinline__ void write_obs(const Env<CPL> &e, const Geo &g, int headcell, float *__restrict__ o,
-                                          int mode, int n, signed char *lds)
+                                          int mode, int n, signed char *lds, float *lds_copy = nullptr)
 {
     const int S = g.S, C = g.C, lane = g.lane;
     if (mode == WURM_OBS_DEFAULT) {
@@ -524,6 +525,11 @@ __device__ __forceinline__ void write_obs(const Env<CPL> &e, const Geo &g, int h
             o[w] = class_rgb(cls, 0, SNAKE);
             o[W2 + w] = class_rgb(cls, 1, SNAKE);
             o[2 * W2 + w] = class_rgb(cls, 2, SNAKE);
+            if (lds_copy) {
+                lds_copy[w] = class_rgb(cls, 0, SNAKE);
+                lds_copy[W2 + w] = class_rgb(cls, 1, SNAKE);
+                lds_copy[2 * W2 + w] = class_rgb(cls, 2, SNAKE);
+            }
         }
         wave_lds_sync();
     } else if (mode == WURM_OBS_ONE_CHANNEL) { // single_snake.py:142-151
@@ -552,6 +558,7 @@ __device__ __forceinline__ void write_obs(const Env<CPL> &e, const Geo &g, int h
         int h = headcell < 0 ? 0 : headcell, f = fcell < 0 ? 0 : fcell;
         int hy = div_size(h, g.rcpS), fy = div_size(f, g.rcpS);
         if (lane < 4) o[lane] = (float)(lane == 0 ? hy : lane == 1 ? h - hy * S : lane == 2 ? fy : f - fy * S);
+        if (lds_copy && lane < 4) lds_copy[lane] = (float)(lane == 0 ? hy : lane == 1 ? h - hy * S : lane == 2 ? fy : f - fy * S);
     }
 }
 
@@ -1886,6 +1893,12 @@ static int check_common(bool snake, const void *envs, long long N, int S, const 
 
 #include "policy_rollout.hpp"
 
+namespace wurm {
+// policy_wide.hip: the fused actor beyond policy_rollout.hpp's domain, and the route of the last policy launch
+int launch_policy_wide(const PolicyArgs &p, int obs_mode, int obs_n, void *stream);
+extern thread_local int policy_route;
+} // namespace wurm
+
 using namespace wurm;
 
 extern "C" {
@@ -2190,7 +2203,8 @@ int wurm_single_policy_rollout(float *envs, const float *obs0, const float *para
                                void *stream)
 {
     if (num_envs < 0 || num_steps < 0 || size < 3) return WURM_ERR_INVALID_ARG;
-    if (size <= 8 || size > 11 || obs_n < 0 || obs_n > 3) return WURM_ERR_UNSUPPORTED;
+    // the reset draw needs 9 x 9; 64 x 64 is the largest grid; n <= 6 is what the crop machinery covers (CROP_NI)
+    if (size <= 8 || size > 64 || obs_n < 0 || obs_n > 6) return WURM_ERR_UNSUPPORTED;
     if (num_envs == 0 || num_steps == 0) return WURM_OK;
     if (!envs || !obs0 || !params || !actions || !probs || !values || !reward || !done || !self_collision ||
         !edge_collision || !obs || !status)
@@ -2200,6 +2214,9 @@ int wurm_single_policy_rollout(float *envs, const float *obs0, const float *para
     p.values = values; p.reward = reward; p.done = done; p.selfc = self_collision; p.edgec = edge_collision;
     p.obs = obs; p.status = status; p.N = num_envs; p.T = num_steps; p.S = size; p.seed = seed; p.call = call0;
     p.env_offset = env_offset;
+    // policy_rollout.hpp's kernels on their domain (WURM_POLICY_WIDE = 1 moves it to policy_wide_kernel), policy_wide.hpp beyond
+    if (size > 11 || obs_n > 3 || opt.policy_wide) return launch_policy_wide(p, WURM_OBS_PARTIAL, obs_n, stream);
+    policy_route = size == 9 && !opt.policy_generic ? 1 : 2;
     return launch_policy_rollout(p, obs_n, stream);
 }
 

@@ -220,5 +220,50 @@ class SimpleGridworld(FastStepMixin):
         self._done_all_false()
         return {'observations': obs, 'rewards': reward, 'dones': flags[0], 'edge_collision': flags[1]}
 
+    def policy_rollout(self, params: torch.Tensor, state: torch.Tensor, num_steps: int, check: bool = True) -> dict:
+        """T iterations of `probs, value = model(state); action = Categorical(probs).sample(); state, reward, done, info =
+        env.step(action); env.reset(done)` in one kernel launch (see SingleSnake.policy_rollout).  The env must be in
+        'positions' mode (the reference's feed-forward agent takes a flat observation; experiments/main.py:129-137) with a
+        start location.  params: `pack_policy_params` of an agent with 4 inputs; state: (num_envs, 4).  Returns (T, N, ...)
+        tensors `actions`, `probs`, `values`, `rewards`, `dones`, `edge_collision`, `observations`, and `state`, `status`.
+        `check=True` synchronises once and raises if any env did not hold exactly one agent and one food."""
+        if self.observation_mode != 'positions':
+            raise NotImplementedError(f'policy_rollout: observation mode {self.observation_mode!r} is an image; the '
+                                      f"feed-forward agent takes 'positions' observations")
+        if self.start_location is None:
+            raise NotImplementedError("Haven't implemented random starting locations")
+        if self.size <= 4 or self.size > 64:
+            raise NotImplementedError(f'policy_rollout: grid size {self.size}; the fused actor serves sizes 5 to 64')
+        N, T, E = self.num_envs, int(num_steps), 4
+        if params.dtype != torch.float32 or params.device != self.device or not params.is_contiguous() or \
+                params.numel() != 64 * E + 64 + 64 * 64 + 64 + 4 * 64 + 4 + 64 + 1:
+            raise RuntimeError('params must be the contiguous fp32 device tensor of pack_policy_params for this observation size')
+        if state.device != self.device or state.numel() != N * E:
+            raise RuntimeError('state must be the current observation of every env on the env device')
+        state = state.to(torch.float32).contiguous()
+        envs = self._state()
+        dev = self.device
+        actions = torch.empty((T, N), dtype=torch.long, device=dev)
+        probs = torch.empty((T, N, 4), dtype=torch.float32, device=dev)
+        values = torch.empty((T, N), dtype=torch.float32, device=dev)
+        reward = torch.empty((T, N), dtype=torch.float32, device=dev)
+        flags = torch.empty((2, T, N), dtype=torch.bool, device=dev)
+        obs = torch.empty((T, N, E), dtype=torch.float32, device=dev)
+        status = torch.empty(N, dtype=torch.uint8, device=dev)
+        rc = _lib.call(dev.index, _lib.lib().wurm_grid_policy_rollout,
+                       _lib.ptr(envs), _lib.ptr(state), _lib.ptr(params), _lib.ptr(actions), _lib.ptr(probs),
+                       _lib.ptr(values), _lib.ptr(reward), _lib.ptr(flags[0]), _lib.ptr(flags[1]), _lib.ptr(obs),
+                       _lib.ptr(status), _lib.i64(N), self.size, _lib.i64(T), int(self.start_location[0]),
+                       int(self.start_location[1]), _lib.u64(self.seed), _lib.u64(self._next_call(2 * T)),
+                       _lib.i64(self.env_offset), _lib.stream_ptr(dev.index))
+        _lib.check(rc, 'SimpleGridworld.policy_rollout')
+        if check and T > 0 and bool(status.any()):
+            raise RuntimeError('policy_rollout: some envs do not hold exactly one agent and one food (status != 0); '
+                               'they were left untouched')
+        self._done_all_false()  # every done env was reset
+        return {'actions': actions, 'probs': probs, 'values': values, 'rewards': reward, 'dones': flags[0],
+                'edge_collision': flags[1], 'observations': obs, 'state': obs[-1] if T > 0 else state.reshape(N, E),
+                'status': status}
+
     def _consistent(self):
         pass

@@ -296,16 +296,22 @@ class SingleSnake(FastStepMixin):
             state, reward, done, info = env.step(action); env.reset(done)
 
         params: `wurm_amd.agents.pack_policy_params(agent)` (inputs -> 64 -> 64 -> {4, 1}); state: the observation the
-        policy acts on first, (num_envs, 3, 2n+1, 2n+1) as returned by reset / step; the env must be in a
-        `partial_n` mode with n <= 3 and size <= 11.  Returns (T, N, ...) tensors: `actions` (sanitised, int64),
+        policy acts on first, (num_envs, 3, 2n+1, 2n+1) for `partial_n` (n <= 6) or (num_envs, 4) for `positions`, as
+        returned by reset / step — the two modes the reference's feed-forward agent takes (experiments/main.py:129-137).
+        Returns (T, N, ...) tensors: `actions` (sanitised, int64),
         `probs`, `values` (no grad — the learner recomputes them from `observations`), `rewards`, `dones`,
         `self_collision`, `edge_collision`, `observations` (what step t returned, i.e. the policy input of step t+1)
         and `state` = observations[-1].  `check=True` synchronises once and raises if any env was outside the
         kernel's domain (not a well-formed snake — only possible if `env.envs` was edited by hand)."""
         m, n, shape = self._mode_info(self.observation_mode)
-        if m != _lib.OBS_PARTIAL or n > 3 or self.size > 11:
-            raise NotImplementedError('policy_rollout: partial_n observation with n <= 3 on grids of size <= 11')
-        E = 3 * (2 * n + 1) ** 2
+        if m not in (_lib.OBS_PARTIAL, _lib.OBS_POSITIONS):
+            raise NotImplementedError(f'policy_rollout: observation mode {self.observation_mode!r} is an image; the '
+                                      f"feed-forward agent takes 'partial_n' or 'positions' observations")
+        if m == _lib.OBS_PARTIAL and n > 6:
+            raise NotImplementedError(f'policy_rollout: partial_{n} crop; the fused actor serves n <= 6')
+        if self.size > 64:
+            raise NotImplementedError(f'policy_rollout: grid size {self.size}; the fused actor serves sizes up to 64')
+        E = 3 * (2 * n + 1) ** 2 if m == _lib.OBS_PARTIAL else 4
         N, T = self.num_envs, int(num_steps)
         if params.dtype != torch.float32 or params.device != self.device or not params.is_contiguous() or \
                 params.numel() != 64 * E + 64 + 64 * 64 + 64 + 4 * 64 + 4 + 64 + 1:
@@ -322,10 +328,10 @@ class SingleSnake(FastStepMixin):
         flags = torch.empty((3, T, N), dtype=torch.bool, device=dev)
         obs = torch.empty((T,) + shape, dtype=torch.float32, device=dev)
         status = torch.empty(N, dtype=torch.uint8, device=dev)
-        rc = _lib.call(dev.index, _lib.lib().wurm_single_policy_rollout,
+        rc = _lib.call(dev.index, _lib.lib().wurm_single_policy_rollout_mode,
                        _lib.ptr(envs), _lib.ptr(state), _lib.ptr(params), _lib.ptr(actions), _lib.ptr(probs),
                        _lib.ptr(values), _lib.ptr(reward), _lib.ptr(flags[0]), _lib.ptr(flags[1]), _lib.ptr(flags[2]),
-                       _lib.ptr(obs), _lib.ptr(status), n, _lib.i64(N), self.size, _lib.i64(T), _lib.u64(self.seed),
+                       _lib.ptr(obs), _lib.ptr(status), m, n, _lib.i64(N), self.size, _lib.i64(T), _lib.u64(self.seed),
                        _lib.u64(self._next_call(2 * T)), _lib.i64(self.env_offset), _lib.stream_ptr(dev.index))
         _lib.check(rc, 'SingleSnake.policy_rollout')
         if check and T > 0 and bool(status.any()):

@@ -319,6 +319,67 @@ def fuzz_policy(rng):
     return desc
 
 
+def fuzz_policy_wide(rng):
+    """policy_wide_kernel (wurm_single_policy_rollout_mode, wurm_grid_policy_rollout) over its whole domain: sizes with
+    weight on the edges of the cells-per-lane buckets, every crop and 'positions', batches up to 2 100 envs (every
+    workgroup shape), start states from tests/policy_states.py or a fresh reset, large keys, two chained launches.
+    WURM_POLICY_WIDE = 1 keeps the old kernels' shapes (S <= 11, n <= 3) on this kernel too."""
+    from tests import policy_states as ps
+    from tests.test_policy_rollout_wide import hip_rollout, oracle_composed
+    snake = rng.rand() < 0.7
+    edges = [9, 11, 12, 16, 17, 22, 23, 32, 33, 39, 40, 45, 46, 55, 56, 64]
+    S = int(rng.choice(edges)) if rng.rand() < 0.6 else int(rng.randint(9 if snake else 5, 65))
+    n = int(rng.randint(0, 7))
+    mode = f'partial_{n}' if snake and rng.rand() < 0.75 else 'positions'
+    E = 4 if mode == 'positions' else 3 * (2 * n + 1) ** 2
+    N = int(rng.choice([1, 5, 64, 100, 300, 1100, 2100]))
+    T = int(rng.choice([1, 3, 7] if N >= 300 else [1, 7, 64, 65, 130]))
+    T = max(1, min(T, 1000000 // (N * E)))   # the oracle is the cost: about 0.2 s per million weights times inputs
+    kind = ['filled', 'fresh', 'crowded'][int(rng.choice(3, p=[0.5, 0.35, 0.15]))]
+    if kind == 'crowded' and (not snake or S > 47):
+        kind = 'filled'
+    scale = float(rng.choice([0.05, 0.3, 1.0, 3.0]))
+    seed, off, call = int(rng.randint(1 << 62)), int(rng.randint(1 << 44)), int(rng.randint(1 << 50))
+    desc = f'policy_wide {"snake" if snake else "grid"} S={S} mode={mode} N={N} T={T} states={kind} scale={scale} seed={seed} off={off} call={call}'
+    if os.environ.get('WURM_FUZZ_VERBOSE'):
+        print('start:', desc, flush=True)
+    grid = None if snake else (int(rng.randint(1, S - 1)), int(rng.randint(1, S - 1)))
+    if snake:
+        if kind == 'fresh':
+            eo = np.zeros((N, 3, S, S), np.float32)
+            _o.single_reset(eo, np.ones(N, np.uint8), 'none', seed, 0, off)
+        else:
+            eo = ps.crowded_snake_states(N, S, rng) if kind == 'crowded' else ps.snake_states(N, S, rng, fill=float(rng.rand()))
+        obs0 = _o.single_observe(eo, mode)
+    else:
+        if kind == 'fresh':
+            eo = np.zeros((N, 2, S, S), np.float32)
+            _o.grid_reset(eo, np.ones(N, np.uint8), grid, 'none', seed, 0, off)
+        else:
+            eo = ps.grid_states(N, S, rng)
+        obs0 = _o.grid_observe(eo, 'positions')
+    obs0 = np.asarray(obs0, np.float32).reshape(N, E)
+    params = (rng.randn(_o.policy_param_count(E)) * scale).astype(np.float32)
+    eh = eo.copy()
+    old = _lib.set_option('WURM_POLICY_WIDE', 1)
+    try:
+        for launch in range(2):
+            if snake and mode != 'positions':
+                ro = _o.single_policy_rollout(eo, obs0, params, T, n, seed, call, off)
+            else:
+                ro = oracle_composed(eo, obs0, params, T, seed, call, off, mode, grid)
+            rh = hip_rollout(eh, obs0, params, T, seed, call, off, mode, grid)
+            assert _lib.lib().wurm_policy_last_route() == b'policy_wide', desc + ' route'
+            assert (rh.pop('status') == 0).all(), desc + ' status'
+            for k in ro:
+                same(ro[k], rh[k], f'{desc} launch {launch} {k}')
+            same(eo, eh, f'{desc} launch {launch} state')
+            obs0, call = ro['obs'][-1], call + 2 * T
+    finally:
+        _lib.set_option('WURM_POLICY_WIDE', old)
+    return desc
+
+
 def fuzz_grid(rng):
     S = int(rng.choice([5, 7, 9, 12, 20, 33, 64]))
     N, T = int(rng.randint(1, 40)), int(rng.randint(5, 80))
@@ -851,10 +912,10 @@ def fuzz_single_mirror_class(rng):
 
 
 FAMILIES = {'single': fuzz_single, 'fused': fuzz_fused, 'resident': fuzz_resident, 'lean': fuzz_lean, 'lane': fuzz_lane,
-            'policy': fuzz_policy, 'grid': fuzz_grid, 'grid_lane': fuzz_grid_lane, 'multi': fuzz_multi, 'multi_resident': fuzz_multi_resident,
+            'policy': fuzz_policy, 'policy_wide': fuzz_policy_wide, 'grid': fuzz_grid, 'grid_lane': fuzz_grid_lane, 'multi': fuzz_multi, 'multi_resident': fuzz_multi_resident,
             'multi_group': fuzz_multi_group, 'multi_mirror_class': fuzz_multi_mirror_class,
             'single_mirror_class': fuzz_single_mirror_class}
-WEIGHTS = {'single': 0.08, 'fused': 0.08, 'resident': 0.13, 'lean': 0.04, 'lane': 0.15, 'policy': 0.03, 'grid': 0.03, 'grid_lane': 0.07,
+WEIGHTS = {'single': 0.08, 'fused': 0.08, 'resident': 0.13, 'lean': 0.04, 'lane': 0.15, 'policy': 0.03, 'policy_wide': 0.05, 'grid': 0.03, 'grid_lane': 0.07,
            'multi': 0.10, 'multi_resident': 0.08, 'multi_group': 0.12, 'multi_mirror_class': 0.07, 'single_mirror_class': 0.07}
 
 

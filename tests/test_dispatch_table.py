@@ -1,4 +1,4 @@
-"""The dispatch table of the SingleSnake / SimpleGridworld entry points (wurm_amd/csrc/single_snake.hip: route_of), one
+"""The dispatch table of the SingleSnake / SimpleGridworld entry points (wurm_amd/csrc/single_launch.hpp: route_of), one
 case per row: which kernel serves a call is a function of (kind, size, batch, observation, injection) alone, read off
 ONE table, and `wurm_single_last_route()` names the row that was taken.  Results never depend on the row (every route
 is compared with the oracle in its own test file); this file pins the table itself.

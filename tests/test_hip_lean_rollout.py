@@ -1,4 +1,4 @@
-"""GPU parity for the lean rollout kernel (`rollout_lean_kernel`, wurm_amd/csrc/single_snake.hip): SingleSnake on
+"""GPU parity for the lean rollout kernel (`rollout_lean_kernel`, wurm_amd/csrc/single_kernels.hpp): SingleSnake on
 grids of at most 128 cells with a `partial_n` crop of n <= 3 or no observation, RNG mode.  It keeps the body channel
 as expiry clocks, takes resets and food draws from per-chunk precomputed Philox blocks and assumes a well-formed
 start state — so it is compared with the CPU oracle (which knows none of that) on every output of every step, over

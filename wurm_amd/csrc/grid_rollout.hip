@@ -1,6 +1,6 @@
 // grid_rollout.hip — SingleSnake rollout for grids of 12 x 12 and larger with the env resident in LDS as a CLOCK GRID.
 //
-// Same contract as rollout_kernel (single_snake.hip): T fused iterations of the caller loop
+// Same contract as rollout_kernel (single_kernels.hpp): T fused iterations of the caller loop
 //     obs, reward, done, info = env.step(actions[t]);  env.reset(done)
 // (tests/test_single_snake_env.py:24-31, experiments/main.py:212-227; step = wurm/envs/single_snake.py:197-304, reset
 // = :322-387), bit-identical to T calls of wurm_single_step / wurm_single_reset.  What differs is where the env lives.
@@ -665,7 +665,7 @@ __global__ __launch_bounds__(256) void grid_rollout_kernel(StepArgs p)
 }
 
 // ---------------------------------------------------------------------------------------------- per-call
-// fused_step_kernel (single_snake.hip) for grids >= 12 x 12 on the clock grid: [reset of the envs flagged in
+// fused_step_kernel (single_kernels.hpp) for grids >= 12 x 12 on the clock grid: [reset of the envs flagged in
 // p.done_in with call = p.pre_call], step (call = p.call), observation, [p.obs_after: the observation reset(done)
 // returns], [p.post_reset: the rebuilt state stored].  The state is read with 16-byte loads into LDS and only the
 // cells the step changed are written back: the decayed body cells, the two head cells, the food cells (a rebuilt env

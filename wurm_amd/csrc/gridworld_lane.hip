@@ -7,7 +7,7 @@
 // 64 consecutive envs with one instruction stream:
 //   * the move, edge test and reward are a handful of integer operations per lane;
 //   * the food respawn after an eaten food and the reset of a finished env are CLOSED FORMS of the same Philox draws the
-//     one-env-per-wave kernels make (single_snake.hip: step_core / reset_core / add_food): the free interior cells are all
+//     one-env-per-wave kernels make (single_device.hpp: step_core / reset_core / add_food): the free interior cells are all
 //     interior cells but the agent's, so "the K-th free cell in row-major order, K = mulhi(word, n_free)" is the interior
 //     cell of index K, shifted by one behind the agent's — no mask, no ballot, no rank select;
 //   * the observation of the wave's envs is one contiguous run (obs is (T, N, ...): consecutive envs are adjacent) that
@@ -33,7 +33,7 @@ struct GridLaneGeo {
 };
 
 // the K-th interior cell in row-major order that is not `taken` (a cell index, or -1), K = mulhi(word, number of such
-// cells); -1 if there is none — add_food of single_snake.hip for a state whose only occupied cell is `taken`
+// cells); -1 if there is none — add_food of single_device.hpp for a state whose only occupied cell is `taken`
 __device__ __forceinline__ int free_interior_cell(const GridLaneGeo &g, int taken, u32 word)
 {
     const int S = g.S, I = g.I;
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(256) void gridworld_lane_rollout_kernel(StepArgs p)
 
 
 // ---- the per-call step (`obs, r, d, info = env.step(a); env.reset(d)`, one launch per iteration) for large batches: the same
-// lane-per-env transition under fused_step_kernel's contract without post_reset (single_snake.hip: fused_step_env) — an env
+// lane-per-env transition under fused_step_kernel's contract without post_reset (single_device.hpp: fused_step_env) — an env
 // flagged in p.done_in is rebuilt in front of the step with call = p.pre_call, the step uses p.call, p.obs is the stepped
 // state's observation, p.obs_after (nullable) what reset(done) will return: the observation once finished envs are rebuilt
 // with call + 1 — not stored, the next launch's postponed reset recreates it from the same counters.  Also serves the plain

@@ -23,6 +23,7 @@
 #pragma once
 
 #include "lane_load.hpp"
+#include "single_device.hpp"
 
 namespace wurm {
 
@@ -134,9 +135,6 @@ __device__ __forceinline__ void lane_observe(const LaneArgs &a, unsigned char *l
         *(float *)(ob + o + 8u * (unsigned)W2) = b;
     }
 }
-
-template <int CPL, bool SNAKE>
-__device__ __forceinline__ void fused_step_env(const StepArgs &p, long long env, signed char *lds);
 
 template <int EPW, int S>
 __global__ __launch_bounds__(256) void lane_step_kernel(LaneArgs a)
@@ -372,7 +370,6 @@ __global__ __launch_bounds__(256) void lane_step_kernel(LaneArgs a)
     }
 }
 
-#ifndef WURM_SINGLE_SNAKE_DEVICE_CODE_ONLY
 static bool lane_step_eligible(const StepArgs &p)
 {
     if (p.S < 9 || p.S * p.S > 128) return false;
@@ -413,6 +410,5 @@ static hipError_t launch_lane_step(const StepArgs &p, hipStream_t stream)
     else go(lane_step_kernel<16, 9>, lane_step_kernel<16, 10>, lane_step_kernel<16, 11>, 16, LaneLds<16>::BYTES);
     return hipGetLastError();
 }
-#endif // WURM_SINGLE_SNAKE_DEVICE_CODE_ONLY
 
 } // namespace wurm

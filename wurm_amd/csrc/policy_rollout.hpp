@@ -1,5 +1,5 @@
-// policy_rollout.hpp — the acting half of the reference's single-agent loop as ONE kernel.
-// Included by single_snake.hip (it uses that file's Env / Geo / Fast machinery); not a standalone header.
+// policy_rollout.hpp — the acting half of the reference's single-agent loop as ONE kernel, on the
+// Env / Geo / Fast machinery of single_device.hpp.
 //
 // Per env (= per wave) and per step, experiments/main.py:207-212,227:
 //     probs, value = model(state)            FeedforwardAgent (wurm/agents/feedforward.py:8-28): E -> 64 -> 64 -> {4, 1}
@@ -23,7 +23,8 @@
 // Every other configuration of the reference's feed-forward experiment (SingleSnake 9 <= S <= 64 with partial_n, n <= 6,
 // or positions; SimpleGridworld positions) runs policy_wide.hpp's kernel, with the same arithmetic.
 #pragma once
-#include <cstdlib>
+
+#include "single_device.hpp"
 
 namespace wurm {
 
@@ -43,6 +44,20 @@ struct PolicyArgs {
     u64 seed, call;
     long long env_offset;
 };
+
+// the argument block of a policy entry point (self_collision == nullptr: SimpleGridworld, which has no such output)
+static PolicyArgs make_policy_args(float *envs, const float *obs0, const float *params, int64_t *actions, float *probs,
+                                   float *values, float *reward, uint8_t *done, uint8_t *self_collision,
+                                   uint8_t *edge_collision, float *obs, uint8_t *status, int64_t num_envs, int size,
+                                   int64_t num_steps, uint64_t seed, uint64_t call0, int64_t env_offset)
+{
+    PolicyArgs p = {};
+    p.envs = envs; p.obs0 = obs0; p.params = params; p.actions = (long long *)actions; p.probs = probs;
+    p.values = values; p.reward = reward; p.done = done; p.selfc = self_collision; p.edgec = edge_collision;
+    p.obs = obs; p.status = status; p.N = num_envs; p.T = num_steps; p.S = size; p.seed = seed; p.call = call0;
+    p.env_offset = env_offset;
+    return p;
+}
 
 __device__ __forceinline__ float exp_spec(float x) // oracle/policy.c: oracle_exp_spec
 {
@@ -89,24 +104,19 @@ __device__ __forceinline__ void tree_sum5(float &a, float &b, float &c, float &d
     e = __int_as_float(lane_value(__float_as_int(e), 63));
 }
 
-// The policy of one wave: lane j is hidden unit j of both layers and column j of the five output rows.
-template <int NOBS>
-struct Policy {
-    static constexpr int W = 2 * NOBS + 1, W2 = W * W, E = 3 * W2, EP = (E + 3) & ~3, H = 64;
+// What every policy of one wave holds whatever its first layer looks like: lane j is hidden unit j of both layers and
+// column j of the five output rows.
+struct PolicyHead {
+    static constexpr int H = 64;
     typedef float f2 __attribute__((ext_vector_type(2)));
-    f2 w1[EP / 2], w2[H / 2]; // (even input, odd input) pairs of the lane's weight rows
+    f2 w2[H / 2]; // (even input, odd input) pairs of the lane's second-layer weight row
     float wp0, wp1, wp2, wp3, wv, bias1, bias2, bp0, bp1, bp2, bp3, bv0;
-    float *lds_x, *lds_h1;    // LDS: x[EP] (policy input, zero padded to a multiple of 4), then the 64 first-layer activations
 
-    __device__ __forceinline__ void load(const float *params, const float *x0, int lane)
+    // params: W1 (64,E) b1 (64) W2 (64,64) b2 (64) Wp (4,64) bp (4) Wv (64) bv (1); everything but W1
+    __device__ __forceinline__ void load(const float *params, int E, int lane)
     {
-        const float *W1 = params, *b1 = W1 + (long long)H * E, *W2p = b1 + H, *b2 = W2p + H * H, *Wp = b2 + H,
-                    *bp = Wp + 4 * H, *Wv = bp + 4, *bv = Wv + H;
-#pragma unroll
-        for (int k = 0; k < EP / 2; ++k) {
-            w1[k].x = 2 * k < E ? W1[(long long)lane * E + 2 * k] : 0.0f;
-            w1[k].y = 2 * k + 1 < E ? W1[(long long)lane * E + 2 * k + 1] : 0.0f;
-        }
+        const float *b1 = params + (long long)H * E, *W2p = b1 + H, *b2 = W2p + H * H, *Wp = b2 + H, *bp = Wp + 4 * H,
+                    *Wv = bp + 4, *bv = Wv + H;
 #pragma unroll
         for (int k = 0; k < H / 2; ++k) {
             w2[k].x = W2p[lane * H + 2 * k];
@@ -115,37 +125,15 @@ struct Policy {
         wp0 = Wp[lane]; wp1 = Wp[H + lane]; wp2 = Wp[2 * H + lane]; wp3 = Wp[3 * H + lane]; wv = Wv[lane];
         bias1 = b1[lane]; bias2 = b2[lane];
         bp0 = bp[0]; bp1 = bp[1]; bp2 = bp[2]; bp3 = bp[3]; bv0 = bv[0];
-        lds_x = (float *)wurm_lds;
-        lds_h1 = lds_x + EP;
-        for (int k = lane; k < EP; k += 64) lds_x[k] = k < E ? x0[k] : 0.0f;
     }
 
-    // probs, value = model(x in LDS) (wurm/agents/feedforward.py:24-28); action = Categorical(probs).sample() with the
-    // uniform u (experiments/main.py:208-210).  All results wave-uniform.
-    __device__ __forceinline__ int act(int lane, float u, float &p0, float &p1, float &p2, float &p3, float &value) const
+    // From the lane's two first-layer chains (acc2: even inputs from bias1, odd inputs from 0) to the sampled action:
+    // probs, value = model(x) (wurm/agents/feedforward.py:24-28); action = Categorical(probs).sample() with the uniform u
+    // (experiments/main.py:208-210).  lds_h1: the wave's 64 first-layer activations.  All results wave-uniform.
+    __device__ __forceinline__ int act(f2 acc2, float *lds_h1, int lane, float u, float &p0, float &p1, float &p2,
+                                       float &p3, float &value) const
     {
-        wave_lds_sync();
-        // The broadcast reads are issued in batches of 8 x 16 bytes and each batch is followed by its 32 fmafs
-        // (sched_barrier): left alone the scheduler keeps two reads in flight and the lone wave eats one LDS latency
-        // per 4 inputs; a whole layer in flight costs 76 registers and with them the occupancy that large batches need.
-        constexpr int BATCH = 8;
-        f2 acc2 = {bias1, 0.0f};
-#pragma unroll
-        for (int k0 = 0; k0 < EP / 4; k0 += BATCH) {
-            float4 xs[BATCH];
-#pragma unroll
-            for (int k = 0; k < BATCH; ++k)
-                if (k0 + k < EP / 4) xs[k] = *(const float4 *)(lds_x + 4 * (k0 + k));
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int k = 0; k < BATCH; ++k)
-                if (k0 + k < EP / 4) {
-                    const f2 lo = {xs[k].x, xs[k].y}, hi = {xs[k].z, xs[k].w};
-                    acc2 = __builtin_elementwise_fma(w1[2 * (k0 + k)], lo, acc2);
-                    acc2 = __builtin_elementwise_fma(w1[2 * (k0 + k) + 1], hi, acc2);
-                }
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        constexpr int BATCH = 8; // (as in the first layer of Policy<NOBS>::act)
         float acc = acc2.x + acc2.y;
         lds_h1[lane] = acc > 0.0f ? acc : 0.0f;
         wave_lds_sync();
@@ -180,11 +168,63 @@ struct Policy {
     }
 };
 
+// The policy with the first layer in registers (n <= 3: at most 148 inputs).
+template <int NOBS>
+struct Policy : PolicyHead {
+    static constexpr int W = 2 * NOBS + 1, W2 = W * W, E = 3 * W2, EP = (E + 3) & ~3;
+    f2 w1[EP / 2];         // (even input, odd input) pairs of the lane's weight row
+    float *lds_x, *lds_h1; // LDS: x[EP] (policy input, zero padded to a multiple of 4), then the 64 first-layer activations
+
+    __device__ __forceinline__ void load(const float *params, const float *x0, int lane)
+    {
+        const float *W1 = params;
+#pragma unroll
+        for (int k = 0; k < EP / 2; ++k) {
+            w1[k].x = 2 * k < E ? W1[(long long)lane * E + 2 * k] : 0.0f;
+            w1[k].y = 2 * k + 1 < E ? W1[(long long)lane * E + 2 * k + 1] : 0.0f;
+        }
+        PolicyHead::load(params, E, lane);
+        lds_x = (float *)wurm_lds;
+        lds_h1 = lds_x + EP;
+        for (int k = lane; k < EP; k += 64) lds_x[k] = k < E ? x0[k] : 0.0f;
+    }
+
+    // the action of PolicyHead::act for the observation in lds_x
+    __device__ __forceinline__ int act(int lane, float u, float &p0, float &p1, float &p2, float &p3, float &value) const
+    {
+        wave_lds_sync();
+        // The broadcast reads are issued in batches of 8 x 16 bytes and each batch is followed by its 32 fmafs
+        // (sched_barrier): left alone the scheduler keeps two reads in flight and the lone wave eats one LDS latency
+        // per 4 inputs; a whole layer in flight costs 76 registers and with them the occupancy that large batches need.
+        constexpr int BATCH = 8;
+        f2 acc2 = {bias1, 0.0f};
+#pragma unroll
+        for (int k0 = 0; k0 < EP / 4; k0 += BATCH) {
+            float4 xs[BATCH];
+#pragma unroll
+            for (int k = 0; k < BATCH; ++k)
+                if (k0 + k < EP / 4) xs[k] = *(const float4 *)(lds_x + 4 * (k0 + k));
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < BATCH; ++k)
+                if (k0 + k < EP / 4) {
+                    const f2 lo = {xs[k].x, xs[k].y}, hi = {xs[k].z, xs[k].w};
+                    acc2 = __builtin_elementwise_fma(w1[2 * (k0 + k)], lo, acc2);
+                    acc2 = __builtin_elementwise_fma(w1[2 * (k0 + k) + 1], hi, acc2);
+                }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        return PolicyHead::act(acc2, lds_h1, lane, u, p0, p1, p2, p3, value);
+    }
+};
+
 // what lane j keeps of step t0 + j, flushed every 64 steps
 struct PolicyRecord {
     int act, flags; // sanitised action; done | self collision << 1 | edge collision << 2 | ate << 3
     float val, p0, p1, p2, p3;
 
+    // SELFC = false: SimpleGridworld, which has no self-collision output (p.selfc == nullptr)
+    template <bool SELFC = true>
     __device__ __forceinline__ void flush(const PolicyArgs &p, long long i) const
     {
         p.actions[i] = (long long)act;
@@ -192,7 +232,7 @@ struct PolicyRecord {
         *(float4 *)(p.probs + 4 * i) = make_float4(p0, p1, p2, p3);
         p.reward[i] = (flags & 8) ? 1.0f : 0.0f;
         p.done[i] = (uint8_t)(flags & 1);
-        p.selfc[i] = (uint8_t)((flags >> 1) & 1);
+        if (SELFC) p.selfc[i] = (uint8_t)((flags >> 1) & 1);
         p.edgec[i] = (uint8_t)((flags >> 2) & 1);
     }
 };
@@ -257,7 +297,7 @@ void policy_rollout_kernel(PolicyArgs p)
     policy_generic_loop<NOBS>(p, env, envp, g, e, f, pol);
 }
 
-// The same loop on the 9x9 machinery of rollout_s9_kernel (single_snake.hip: cell codes 8 * row + column, one lane per
+// The same loop on the 9x9 machinery of rollout_s9_kernel (single_kernels.hpp: cell codes 8 * row + column, one lane per
 // interior cell, ring / body / food in one bit test, crop liveness from a per-lane table).  Envs that are well formed
 // but outside that kernel's extra preconditions (body or food on the ring) take the generic loop.
 template <int NOBS>
@@ -447,37 +487,5 @@ void policy_rollout_s9_kernel(PolicyArgs p)
         envp[2 * S * S + my_cell] = (float)max(ex - T, 0);
     }
 }
-
-#ifndef WURM_SINGLE_SNAKE_DEVICE_CODE_ONLY // (policy_wide.hip includes this file for the pieces above only)
-static int launch_policy_rollout(const PolicyArgs &p, int obs_n, void *stream)
-{
-    const int W2 = (2 * obs_n + 1) * (2 * obs_n + 1), EP = (3 * W2 + 3) & ~3;
-    const size_t lds = (size_t)(EP + 64) * sizeof(float);
-    dim3 grid((unsigned)p.N), block(64);
-    hipStream_t st = (hipStream_t)stream;
-    (void)hipGetLastError();
-    const bool s9 = p.S == 9 && !opt.policy_generic; // (debug switch: time / test the generic loop on 9x9 grids)
-    switch (obs_n) {
-    case 0:
-        if (s9) WURM_LAUNCH(policy_rollout_s9_kernel<0>, grid, block, lds, st, p);
-        else WURM_LAUNCH(policy_rollout_kernel<0>, grid, block, lds, st, p);
-        break;
-    case 1:
-        if (s9) WURM_LAUNCH(policy_rollout_s9_kernel<1>, grid, block, lds, st, p);
-        else WURM_LAUNCH(policy_rollout_kernel<1>, grid, block, lds, st, p);
-        break;
-    case 2:
-        if (s9) WURM_LAUNCH(policy_rollout_s9_kernel<2>, grid, block, lds, st, p);
-        else WURM_LAUNCH(policy_rollout_kernel<2>, grid, block, lds, st, p);
-        break;
-    case 3:
-        if (s9) WURM_LAUNCH(policy_rollout_s9_kernel<3>, grid, block, lds, st, p);
-        else WURM_LAUNCH(policy_rollout_kernel<3>, grid, block, lds, st, p);
-        break;
-    default: return WURM_ERR_UNSUPPORTED;
-    }
-    return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
-}
-#endif
 
 } // namespace wurm

@@ -1,13 +1,7 @@
 // policy_wide.hip — translation unit of the fused acting loop for every configuration the reference's feed-forward
 // experiment accepts (policy_wide.hpp) and of its entry points: the observation-mode entry of SingleSnake, the
-// SimpleGridworld one, and the route query of the policy entry points.  Like lane_wide.hip it needs the device code of
-// single_snake.hip and none of its kernels or entry points; wurm_single_policy_rollout (single_snake.hip) calls
+// SimpleGridworld one, and the route query of the policy entry points.  wurm_single_policy_rollout (single_snake.hip) calls
 // launch_policy_wide for the shapes outside policy_rollout.hpp's domain.
-#define WURM_SINGLE_SNAKE_DEVICE_CODE_ONLY
-#include <algorithm>
-
-#include "single_snake.hip"
-#include "policy_rollout.hpp"
 #include "policy_wide.hpp"
 
 namespace wurm {
@@ -15,15 +9,6 @@ namespace wurm {
 // which kernel served the CALLING THREAD's last policy launch (wurm_policy_last_route): 0 none yet, 1 policy_rollout_s9_kernel,
 // 2 policy_rollout_kernel, 3 policy_wide_kernel.  Set by both translation units of the policy entry points.
 thread_local int policy_route = 0;
-
-static int cpl_of(int S)
-{
-    const int need = (S * S + 63) / 64;
-    const int opts[] = {2, 4, 8, 16, 24, 32, 48, 64};
-    for (int o : opts)
-        if (need <= o) return o;
-    return -1;
-}
 
 // the SingleSnake launch (obs_mode WURM_OBS_PARTIAL or WURM_OBS_POSITIONS); arguments already validated
 int launch_policy_wide(const PolicyArgs &p, int obs_mode, int obs_n, void *stream)
@@ -34,7 +19,7 @@ int launch_policy_wide(const PolicyArgs &p, int obs_mode, int obs_n, void *strea
     a.obs_n = obs_mode == WURM_OBS_PARTIAL ? obs_n : 0;
     a.E = obs_mode == WURM_OBS_PARTIAL ? 3 * (2 * obs_n + 1) * (2 * obs_n + 1) : 4;
     policy_route = 3;
-    return launch_policy_wide_cpl<true>(a, cpl_of(p.S), (hipStream_t)stream);
+    return launch_policy_wide_cpl<true>(a, pick_cpl(p.S), (hipStream_t)stream);
 }
 
 } // namespace wurm
@@ -72,11 +57,8 @@ int wurm_single_policy_rollout_mode(float *envs, const float *obs0, const float 
     if (!envs || !obs0 || !params || !actions || !probs || !values || !reward || !done || !self_collision ||
         !edge_collision || !obs || !status)
         return WURM_ERR_INVALID_ARG;
-    PolicyArgs p = {};
-    p.envs = envs; p.obs0 = obs0; p.params = params; p.actions = (long long *)actions; p.probs = probs;
-    p.values = values; p.reward = reward; p.done = done; p.selfc = self_collision; p.edgec = edge_collision;
-    p.obs = obs; p.status = status; p.N = num_envs; p.T = num_steps; p.S = size; p.seed = seed; p.call = call0;
-    p.env_offset = env_offset;
+    const PolicyArgs p = make_policy_args(envs, obs0, params, actions, probs, values, reward, done, self_collision,
+                                          edge_collision, obs, status, num_envs, size, num_steps, seed, call0, env_offset);
     return launch_policy_wide(p, WURM_OBS_POSITIONS, 0, stream);
 }
 
@@ -93,17 +75,14 @@ int wurm_grid_policy_rollout(float *envs, const float *obs0, const float *params
         !status)
         return WURM_ERR_INVALID_ARG;
     PolicyWideArgs a = {};
-    PolicyArgs &p = a.p;
-    p.envs = envs; p.obs0 = obs0; p.params = params; p.actions = (long long *)actions; p.probs = probs;
-    p.values = values; p.reward = reward; p.done = done; p.selfc = nullptr; p.edgec = edge_collision;
-    p.obs = obs; p.status = status; p.N = num_envs; p.T = num_steps; p.S = size; p.seed = seed; p.call = call0;
-    p.env_offset = env_offset;
+    a.p = make_policy_args(envs, obs0, params, actions, probs, values, reward, done, nullptr, edge_collision, obs, status,
+                           num_envs, size, num_steps, seed, call0, env_offset);
     a.obs_mode = WURM_OBS_POSITIONS;
     a.E = 4;
     a.start_y = start_y;
     a.start_x = start_x;
     policy_route = 3;
-    return launch_policy_wide_cpl<false>(a, cpl_of(size), (hipStream_t)stream);
+    return launch_policy_wide_cpl<false>(a, pick_cpl(size), (hipStream_t)stream);
 }
 
 } // extern "C"

@@ -3,8 +3,6 @@
 // 'partial_n'):
 //   SingleSnake      9 <= S <= 64, partial_n with 0 <= n <= 6 (E = 3 (2n+1)^2 <= 507) or positions (E = 4);
 //   SimpleGridworld  5 <= S <= 64, positions (E = 4), the fixed start location.
-// Included by policy_wide.hip after single_snake.hip (device code only) and policy_rollout.hpp (PolicyArgs, exp_spec,
-// tree_sum5); not a standalone header.
 //
 // The loop is rollout_generic's (one env per wave, Env<CPL> at every cells-per-lane bucket, the scalar carry of `Fast`
 // for snakes) with the action tape replaced by the policy: per step, probs / value / sampled action from the observation
@@ -24,6 +22,10 @@
 // (at most 8), fewer for small batches so that the workgroups still spread over the CUs.
 #pragma once
 
+#include <algorithm>
+
+#include "policy_rollout.hpp"
+
 namespace wurm {
 
 struct PolicyWideArgs {
@@ -34,34 +36,22 @@ struct PolicyWideArgs {
     int wpb, wave_bytes; // waves per workgroup, LDS bytes per wave
 };
 
-// the policy of one wave with the first layer in LDS (lane j = hidden unit j of both layers, column j of the heads)
-struct PolicyWide {
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    f2 w2[32];
-    float wp0, wp1, wp2, wp3, wv, bias1, bias2, bp0, bp1, bp2, bp3, bv0;
+// the policy of one wave with the first layer in LDS
+struct PolicyWide : PolicyHead {
     const f2 *w1;   // LDS: (EP / 2, 64) pairs, shared by the workgroup
     float *x, *h1;  // LDS of this wave: x[EP] (input, zero padded), h1[64]
     int EP;
 
     __device__ __forceinline__ void load(const float *params, int E, int ep, int lane, const f2 *w1_lds, float *x_lds)
     {
-        const float *b1 = params + (long long)64 * E, *W2p = b1 + 64, *b2 = W2p + 64 * 64, *Wp = b2 + 64,
-                    *bp = Wp + 4 * 64, *Wv = bp + 4, *bv = Wv + 64;
-#pragma unroll
-        for (int k = 0; k < 32; ++k) {
-            w2[k].x = W2p[lane * 64 + 2 * k];
-            w2[k].y = W2p[lane * 64 + 2 * k + 1];
-        }
-        wp0 = Wp[lane]; wp1 = Wp[64 + lane]; wp2 = Wp[128 + lane]; wp3 = Wp[192 + lane]; wv = Wv[lane];
-        bias1 = b1[lane]; bias2 = b2[lane];
-        bp0 = bp[0]; bp1 = bp[1]; bp2 = bp[2]; bp3 = bp[3]; bv0 = bv[0];
+        PolicyHead::load(params, E, lane);
         w1 = w1_lds;
         x = x_lds;
         h1 = x_lds + ep;
         EP = ep;
     }
 
-    // probs, value = model(x in LDS), action = Categorical(probs).sample() with the uniform u; all results wave-uniform
+    // the action of PolicyHead::act for the observation in x
     __device__ __forceinline__ int act(int lane, float u, float &p0, float &p1, float &p2, float &p3, float &value) const
     {
         wave_lds_sync();
@@ -83,37 +73,7 @@ struct PolicyWide {
                 acc2 = __builtin_elementwise_fma(ws[2 * i + 1], hi, acc2);
             }
         }
-        float acc = acc2.x + acc2.y;
-        h1[lane] = acc > 0.0f ? acc : 0.0f;
-        wave_lds_sync();
-        acc2.x = bias2;
-        acc2.y = 0.0f;
-#pragma unroll
-        for (int k0 = 0; k0 < 16; k0 += 8) {
-            float4 hs[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) hs[k] = *(const float4 *)(h1 + 4 * (k0 + k));
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const f2 lo = {hs[k].x, hs[k].y}, hi = {hs[k].z, hs[k].w};
-                acc2 = __builtin_elementwise_fma(w2[2 * (k0 + k)], lo, acc2);
-                acc2 = __builtin_elementwise_fma(w2[2 * (k0 + k) + 1], hi, acc2);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        acc = acc2.x + acc2.y;
-        const float h2 = acc > 0.0f ? acc : 0.0f;
-        float t0 = wp0 * h2, t1 = wp1 * h2, t2 = wp2 * h2, t3 = wp3 * h2, t4 = wv * h2;
-        tree_sum5(t0, t1, t2, t3, t4);
-        const float l0 = t0 + bp0, l1 = t1 + bp1, l2 = t2 + bp2, l3 = t3 + bp3;
-        value = t4 + bv0;
-        const float m = fmaxf(fmaxf(l0, l1), fmaxf(l2, l3));
-        const float e0 = exp_spec(l0 - m), e1 = exp_spec(l1 - m), e2 = exp_spec(l2 - m), e3 = exp_spec(l3 - m);
-        const float rs = 1.0f / (((e0 + e1) + e2) + e3);
-        p0 = e0 * rs; p1 = e1 * rs; p2 = e2 * rs; p3 = e3 * rs;
-        const float c0 = p0, c1 = c0 + p1, c2 = c1 + p2;
-        return uniform((u >= c0 ? 1 : 0) + (u >= c1 ? 1 : 0) + (u >= c2 ? 1 : 0));
+        return PolicyHead::act(acc2, h1, lane, u, p0, p1, p2, p3, value);
     }
 };
 
@@ -195,8 +155,7 @@ __global__ __launch_bounds__(64 * policy_wide_max_wpb<CPL>()) void policy_wide_k
         const int nt = (int)min((long long)64, p.T - t0);
         const long long my_t = t0 + lane;
         const float my_u = u01(rng_words(p.seed, p.call + 2ull * (u64)my_t, env_id, RNG_POLICY, 0).w[0]);
-        int my_act = 0, my_flags = 0; // flags: done | self collision << 1 | edge collision << 2 | ate << 3
-        float my_val = 0.0f, my_p0 = 0.0f, my_p1 = 0.0f, my_p2 = 0.0f, my_p3 = 0.0f;
+        PolicyRecord rec = {0, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         for (int j = 0; j < nt; ++j, obs_t += obs_stride, call += 2) {
             float p0, p1, p2, p3, value;
             const int act = pol.act(lane, __int_as_float(lane_value(__float_as_int(my_u), j)), p0, p1, p2, p3, value);
@@ -218,21 +177,12 @@ __global__ __launch_bounds__(64 * policy_wide_max_wpb<CPL>()) void policy_wide_k
                 if (out.done) reset_core<CPL, false>(e, g, p.seed, call + 1ull, env_id, nullptr, a.start_y, a.start_x);
             }
             if (lane == j) {
-                my_act = (int)out.action;
-                my_flags = out.done | (out.selfc << 1) | (out.edgec << 2) | (out.reward != 0.0f ? 8 : 0);
-                my_val = value; my_p0 = p0; my_p1 = p1; my_p2 = p2; my_p3 = p3;
+                rec.act = (int)out.action;
+                rec.flags = out.done | (out.selfc << 1) | (out.edgec << 2) | (out.reward != 0.0f ? 8 : 0);
+                rec.val = value; rec.p0 = p0; rec.p1 = p1; rec.p2 = p2; rec.p3 = p3;
             }
         }
-        if (lane < nt) {
-            const long long i = my_t * p.N + env;
-            p.actions[i] = (long long)my_act;
-            p.values[i] = my_val;
-            *(float4 *)(p.probs + 4 * i) = make_float4(my_p0, my_p1, my_p2, my_p3);
-            p.reward[i] = (my_flags & 8) ? 1.0f : 0.0f;
-            p.done[i] = (uint8_t)(my_flags & 1);
-            if (SNAKE) p.selfc[i] = (uint8_t)((my_flags >> 1) & 1);
-            p.edgec[i] = (uint8_t)((my_flags >> 2) & 1);
-        }
+        if (lane < nt) rec.template flush<SNAKE>(p, my_t * p.N + env);
     }
     if constexpr (SNAKE) fast_sync_bits<CPL>(e, g, f);
     store_state<CPL, SNAKE>(envp, g, e);

@@ -1,6 +1,9 @@
-// single_grid.hip — the SimpleGridworld half of single_snake.hip's kernels (launch<false>: step / reset / observe / fused step /
-// rollout / flagged kernels of the two-channel state at every cells-per-lane), compiled as a translation unit of its own so
-// that the two halves build side by side.  Everything else of that file — the SingleSnake half, the entry points — is
-// compiled with single_snake.hip itself.
-#define WURM_TU_GRID
-#include "single_snake.hip"
+// single_grid.hip — the SimpleGridworld half of the one-env-per-wave kernels: launch<false> and every kernel it instantiates
+// (single_snake.hip holds launch<true> and the entry points), so that the two halves compile side by side.
+#include "single_launch.hpp"
+
+namespace wurm {
+
+template int launch<false>(Kind, StepArgs, void *);
+
+} // namespace wurm

@@ -1,5 +1,5 @@
 // step_args.hpp — the kernel argument block and action accessors shared by the SingleSnake / SimpleGridworld
-// translation units (single_snake.hip, grid_rollout.hip).
+// translation units (single_device.hpp and what is built on it, grid_rollout.hip, gridworld_lane.hip).
 #pragma once
 
 #include "wurm_device.hpp"

@@ -1,0 +1,60 @@
+#!/usr/bin/env python3
+"""The single-agent A2C experiment of the reference (experiments/main.py:194-247) with BOTH halves in HIP: the acting
+half is `env.policy_rollout(learner.params, state, update_steps)` (policy -> sample -> step -> reset inside the env
+kernel, as in examples/a2c_fused_actor.py), the learning half is `learner.update(state, out)`: forward, return scan, loss,
+backward pass, clip_grad_norm_ and Adam in three launches (wurm_amd.rl.FusedA2CLearner).  Per update the host issues four
+kernel launches and reads nothing back; the loss is copied to the host only for a log line.
+
+    python examples/a2c_fused_learner.py --num-envs 512 --steps 20000
+"""
+import argparse
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from wurm_amd.agents import FeedforwardAgent  # noqa: E402
+from wurm_amd.envs import SingleSnake  # noqa: E402
+from wurm_amd.rl import FusedA2CLearner  # noqa: E402
+
+
+def run(num_envs=512, size=9, observation='partial_2', steps=20000, update_steps=5, gamma=0.99, lr=1e-3, entropy=0.01,
+        log_interval=2000, seed=0, device='cuda', verbose=True):
+    torch.manual_seed(seed)
+    env = SingleSnake(num_envs=num_envs, size=size, observation_mode=observation, device=device, seed=seed)
+    state = env.reset()                                                     # main.py:195
+    model = FeedforwardAgent(num_actions=4, num_layers=2, hidden_units=64, num_inputs=state[0].numel()).to(device)
+    learner = FusedA2CLearner(model, lr=lr, gamma=gamma, entropy_coef=entropy, max_grad_norm=0.5)
+    totals = torch.zeros(2, dtype=torch.float64, device=device)             # rewards, dones since the last log line
+    history, t0, last = [], time.perf_counter(), 0
+    for i_step in range(update_steps, steps + 1, update_steps):
+        out = env.policy_rollout(learner.params, state, update_steps, check=False)              # :207-227, fused
+        res = learner.update(state, out)                                                         # :229-245, fused
+        state = out['state']
+        totals += torch.stack([out['rewards'].sum(dtype=torch.float64), out['dones'].sum(dtype=torch.float64)])
+        if i_step % log_interval < update_steps or i_step + update_steps > steps:
+            s = totals.cpu().tolist()
+            totals.zero_()
+            n = (i_step - last) * num_envs
+            dt, last = time.perf_counter() - t0, i_step
+            loss = res['value_loss'] + res['policy_loss'] - entropy * res['entropy']             # :239-242
+            row = dict(step=i_step, env_steps_per_s=i_step * num_envs / dt, reward_rate=s[0] / n, done_rate=s[1] / n,
+                       loss=float(loss))
+            history.append(row)
+            if verbose:
+                print(' '.join(f'{k}={v:.4g}' for k, v in row.items()))
+    return history
+
+
+if __name__ == '__main__':
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--num-envs', type=int, default=512)
+    ap.add_argument('--size', type=int, default=9)
+    ap.add_argument('--observation', default='partial_2')
+    ap.add_argument('--steps', type=int, default=20000)
+    ap.add_argument('--update-steps', type=int, default=5)
+    ap.add_argument('--lr', type=float, default=1e-3)
+    args = ap.parse_args()
+    run(args.num_envs, args.size, args.observation, args.steps, args.update_steps, lr=args.lr)

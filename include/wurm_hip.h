@@ -577,6 +577,53 @@ int wurm_a2c_returns_backward(const float *grad_returns, const uint8_t *dones, f
 int wurm_single_stats(const float *envs, const float *reward, const uint8_t *done, const uint8_t *self_collision,
                       const uint8_t *edge_collision, double *accum, int64_t num_envs, int size, void *stream);
 
+/* ------------------------------------------------------------------------------------------- fused A2C learner
+ * One update of the 2 x 64 feed-forward actor-critic (wurm_amd/agents.py) from the outputs of a policy rollout:
+ * batched forward, the n-step return scan of wurm_a2c_returns (use_gae = 0), the loss of experiments/main.py:236-242
+ * with A2C(gamma) defaults, its gradient, clip_grad_norm_ and torch.optim.Adam — three launches, no host
+ * synchronisation, no atomics (bit-identical from run to run).  Kernels: wurm_amd/csrc/a2c_learner.hpp.
+ *   params (P) as pack_policy_params, P = 64 E + 64 + 4096 + 64 + 256 + 4 + 64 + 1;  obs0 (N,E) the input of step 0;
+ *   obs (T,N,E) what step t returned (the input of step t + 1; obs[T-1] is the bootstrap input and gets no gradient);
+ *   actions (T,N) int64 in 0..3;  rewards (T,N) fp32;  dones (T,N) bytes.
+ *   loss = mean l(v - R) - mean((R - v) log p~[a]) - entropy_coef * mean H, l = value_loss_kind, log p~ =
+ *   log(clamp(p, eps32, 1 - eps32)), H = - sum_k p_k log p~_k, means over the N T samples, R and R - v constants.
+ *   num_inputs: 3 (2n+1)^2 for n <= 6 ('partial_n') or 4 ('positions'); anything else is WURM_ERR_UNSUPPORTED. */
+#define WURM_A2C_SMOOTH_L1 0 /* F.smooth_l1_loss, beta = 1 */
+#define WURM_A2C_MSE 1       /* (v - R)^2 */
+
+/* Bytes of the caller-owned workspace of the two calls below (0 for an unsupported shape): one partial gradient per
+ * workgroup (at most 256 of them) and eight parked floats (32 bytes) per row.  The workspace must be 16-byte aligned. */
+int64_t wurm_a2c_ff_workspace_bytes(int64_t num_envs, int64_t num_steps, int num_inputs);
+
+/* grad (P): the unclipped gradient;  losses (3): value loss, policy loss, mean entropy;  values_out: nullable, (T,N),
+ * the value of every policy input (what the rollout's own `values` are to fp32 rounding). */
+int wurm_a2c_ff_grad(const float *params, const float *obs0, const float *obs, const int64_t *actions,
+                     const float *rewards, const uint8_t *dones, float gamma, float entropy_coef, int value_loss_kind,
+                     float *grad, float *losses, float *values_out, void *workspace, int64_t workspace_bytes,
+                     int64_t num_envs, int64_t num_steps, int num_inputs, void *stream);
+
+/* clip_grad_norm_(max_grad_norm) + one torch.optim.Adam step (no weight decay, no amsgrad) in place, `step` counting
+ * from 1.  grad is not modified; grad_norm (1, nullable) receives ||grad||_2 before clipping; max_grad_norm <= 0: no
+ * clipping.  lr, beta1, beta2 and eps are taken as the shortest decimal that rounds to the float given (0.999f means
+ * 0.999), so that 1 - beta2 and the bias corrections are those of torch's double-valued hyper-parameters. */
+int wurm_a2c_ff_apply(float *params, const float *grad, float *exp_avg, float *exp_avg_sq, float *grad_norm,
+                      int64_t step, float lr, float beta1, float beta2, float eps, float max_grad_norm,
+                      int64_t num_params, void *stream);
+
+/* The double that wurm_a2c_ff_apply / _update compute with for the float hyper-parameter x: the shortest decimal (at
+ * most 9 digits) that rounds to x, x itself if there is none or x is not finite.  A caller whose value really is
+ * 0.99900001287460327 cannot say so through a float; it gets the arithmetic of 0.999. */
+int wurm_a2c_ff_hyper_parameter(float x, double *value);
+
+/* wurm_a2c_ff_grad followed by wurm_a2c_ff_apply in one call: the same kernels, bit-identical results, grad and
+ * losses still written. */
+int wurm_a2c_ff_update(float *params, const float *obs0, const float *obs, const int64_t *actions,
+                       const float *rewards, const uint8_t *dones, float gamma, float entropy_coef,
+                       int value_loss_kind, float *grad, float *losses, float *values_out, void *workspace,
+                       int64_t workspace_bytes, int64_t num_envs, int64_t num_steps, int num_inputs, float *exp_avg,
+                       float *exp_avg_sq, float *grad_norm, int64_t step, float lr, float beta1, float beta2, float eps,
+                       float max_grad_norm, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

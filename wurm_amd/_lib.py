@@ -29,6 +29,8 @@ SYMBOLS = [
     'wurm_multi_colours', 'wurm_orientations',
     'wurm_a2c_returns', 'wurm_a2c_returns_backward', 'wurm_single_stats', 'wurm_single_policy_rollout',
     'wurm_single_policy_rollout_mode', 'wurm_grid_policy_rollout', 'wurm_policy_last_route',
+    'wurm_a2c_ff_workspace_bytes', 'wurm_a2c_ff_grad', 'wurm_a2c_ff_apply', 'wurm_a2c_ff_update',
+    'wurm_a2c_ff_hyper_parameter',
 ]
 
 

@@ -1,0 +1,460 @@
+// a2c_learner.hpp — one A2C update of the 2 x 64 feed-forward actor-critic as three kernels:
+//   a2c_ff_main_kernel    forward, return scan, loss derivatives and backward pass of a block of envs per workgroup;
+//                         every workgroup writes ITS gradient (P floats) and loss sums to the caller's workspace
+//   a2c_ff_reduce_kernel  sums the workgroups' partials in workgroup order into grad / losses
+//   a2c_ff_apply_kernel   ||g|| in a fixed order (every workgroup computes the same bits), clip, Adam
+// No float atomics anywhere: two runs on the same inputs give the same bits.
+//
+// Main kernel.  A workgroup (256 threads) owns the envs [wg N / G, (wg + 1) N / G) with all T + 1 rows of each (the T
+// policy inputs and the bootstrap input), in the local order row = t * nenv + i, cut into tiles of 64 rows.  All
+// products are 64-row tiles against 64-wide weights out of LDS: a thread owns a 4 x 4 block of the 64 x 64 result and
+// feeds it with 16-byte LDS reads (8 reads per 64 fmaf).  Rows of LDS images are 68 floats apart, which keeps the 16
+// rows a 16-lane group reads on 16 different bank quartets.  W1 and the inputs go through LDS in chunks of 64 inputs,
+// zero-padded to a multiple of 16 on both sides, so a padded product is an exact zero.
+//   pass 1: forward of every tile -> softmax probabilities and value of every row, parked in the workspace
+//           (6 floats per row; written and read by this workgroup only)
+//   scan:   one thread per env walks its T rows backwards (the fp32 expression of rl.hip: a2c_returns_kernel)
+//   pass 2: forward of the tile again (skipped when the workgroup has a single tile: H1 / H2 are still in LDS), the loss
+//           derivatives per row, then dZ2 = (dz Wp + dv Wv) [H2 > 0], dW2 += dZ2^T H1, dZ1 = (dZ2 W2) [H1 > 0],
+//           dW1 += dZ1^T X.  dW2, the head and bias gradients accumulate in registers over the tiles; dW1 (up to 128 floats
+//           per thread at E = 507) accumulates in the workgroup's own partial, read and written by the same thread.
+// Rows past the workgroup's last row and the bootstrap rows get dz = dv = 0, so they add exact zeros everywhere.
+// The products are fp32 fmaf chains in a fixed order (the build has -ffp-contract=off: every fmaf here is explicit); the
+// bias and loss sums and the sum over the workgroups run in double.
+#pragma once
+#include "wurm_device.hpp"
+
+namespace wurm {
+namespace a2c {
+
+constexpr int HID = 64;      // hidden units of both layers
+constexpr int TILE = 64;     // rows per tile
+constexpr int LD = 68;       // floats between rows of an LDS image
+constexpr int CHUNK = 64;    // inputs per pass through LDS
+constexpr int THREADS = 256;
+constexpr int ROW_FLOATS = 8; // parked per row: p0..p3, v, R (+ 2 unused: 32-byte rows)
+constexpr int MAX_GROUPS = 256;
+
+__host__ __device__ inline long long num_params(int E) { return 64LL * E + 64 + 4096 + 64 + 256 + 4 + 64 + 1; }
+__host__ __device__ inline int padded_inputs(int E) { return (E + 15) & ~15; }
+// floats per workgroup partial: dW1 with its rows padded to padded_inputs(E) (16-byte stores), the other seven blocks
+// as they are packed, then the three loss sums; rounded up to 16 bytes
+__host__ __device__ inline long long partial_stride(int E)
+{
+    return (64LL * padded_inputs(E) + (num_params(E) - 64LL * E) + 3 + 3) & ~3LL;
+}
+
+struct MainArgs {
+    const float *params, *obs0, *obs;
+    const long long *actions;
+    const float *rewards;
+    const uint8_t *dones;
+    float *values_out; // nullable
+    float *partials;   // (G, partial_stride)
+    float *rows;       // (N (T + 1), ROW_FLOATS)
+    long long N, T;
+    int E, G, loss_kind;
+    float gamma, entropy_coef, inv_B;
+};
+
+// acc[i][j] += sum_k A[4 tr + i][k] * B[tj + 16 j][k], k < K (a multiple of 4)
+__device__ __forceinline__ void gemm_nt(const float *A, const float *B, int K, int tr, int tj, float (&acc)[4][4])
+{
+    const float *pa = A + 4 * tr * LD, *pb = B + tj * LD;
+    for (int k = 0; k < K; k += 4) {
+        float4 a[4], b[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            a[i] = *reinterpret_cast<const float4 *>(pa + i * LD + k);
+            b[i] = *reinterpret_cast<const float4 *>(pb + 16 * i * LD + k);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float s = acc[i][j];
+                s = fmaf(a[i].x, b[j].x, s);
+                s = fmaf(a[i].y, b[j].y, s);
+                s = fmaf(a[i].z, b[j].z, s);
+                acc[i][j] = fmaf(a[i].w, b[j].w, s);
+            }
+    }
+}
+
+// acc[i][j] += sum_r A[r][4 tr + i] * B[r][4 tj + j], r < 64
+__device__ __forceinline__ void gemm_tn(const float *A, const float *B, int tr, int tj, float (&acc)[4][4])
+{
+    const float *pa = A + 4 * tr, *pb = B + 4 * tj;
+#pragma unroll 4
+    for (int r = 0; r < TILE; ++r) {
+        const float4 a = *reinterpret_cast<const float4 *>(pa + r * LD);
+        const float4 b = *reinterpret_cast<const float4 *>(pb + r * LD);
+        const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[i][j] = fmaf(av[i], bv[j], acc[i][j]);
+    }
+}
+
+__device__ __forceinline__ float wave_sum_f32(float v) // fixed butterfly order: the same bits every run
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(MainArgs g)
+{
+    __shared__ __attribute__((aligned(16))) float Xs[TILE * LD], W1s[HID * LD], W2s[HID * LD], W2Ts[HID * LD];
+    __shared__ __attribute__((aligned(16))) float H1s[TILE * LD], H2s[TILE * LD], dZ2s[TILE * LD], dZ1s[TILE * LD];
+    __shared__ __attribute__((aligned(16))) float Wps[4 * HID], Wvs[HID], b1s[HID], b2s[HID], zs[TILE * 8];
+    __shared__ float bhs[8];
+    __shared__ const float *row_x[TILE]; // the row's input, nullptr past the workgroup's last row
+    __shared__ long long row_env[TILE];
+    __shared__ long long row_t[TILE];
+
+    const int tid = (int)threadIdx.x, tr = tid >> 4, tj = tid & 15, lane = tid & 63, part = tid >> 6;
+    const long long N = g.N, T = g.T;
+    const int E = g.E, Epad = padded_inputs(E);
+    const long long e0 = (long long)blockIdx.x * N / g.G, e1 = ((long long)blockIdx.x + 1) * N / g.G;
+    const long long nenv = e1 - e0, rows = nenv * (T + 1), ntiles = (rows + TILE - 1) / TILE;
+    const float *W1 = g.params, *b1 = W1 + 64LL * E, *W2 = b1 + 64, *b2 = W2 + 4096, *Wp = b2 + 64, *bp = Wp + 256,
+                *Wv = bp + 4, *bv = Wv + 64;
+    float *parked = g.rows + e0 * (T + 1) * ROW_FLOATS;
+    float *partial = g.partials + (long long)blockIdx.x * partial_stride(E);
+
+    for (int idx = tid; idx < HID * HID; idx += THREADS) {
+        const int j = idx >> 6, k = idx & 63;
+        const float w = W2[idx];
+        W2s[j * LD + k] = w;
+        W2Ts[k * LD + j] = w;
+    }
+    Wps[tid] = Wp[tid];
+    if (tid < HID) {
+        b1s[tid] = b1[tid];
+        b2s[tid] = b2[tid];
+        Wvs[tid] = Wv[tid];
+    }
+    if (tid < 4) bhs[tid] = bp[tid];
+    if (tid == 4) bhs[4] = bv[0];
+
+    int xs_c0 = -1; // the chunk of the current tile that Xs holds
+
+    // all CHUNK columns of Xs are written: the columns past the last chunk's end are zeros, as the padded ones are
+    // (gemm_tn reads all 64)
+    auto load_x = [&](int c0) {
+        for (int idx = tid; idx < TILE * CHUNK; idx += THREADS) {
+            const int r = idx / CHUNK, k = idx % CHUNK, e = c0 + k;
+            const float *x = row_x[r];
+            Xs[r * LD + k] = (x != nullptr && e < E) ? x[e] : 0.0f;
+        }
+        xs_c0 = c0;
+    };
+
+    // rows of tile -> H1s, H2s (post-ReLU; a unit is live where its entry is > 0)
+    auto forward = [&](long long tile) {
+        __syncthreads(); // everybody is done with the previous tile's row table and images
+        if (tid < TILE) {
+            const long long lr = tile * TILE + tid;
+            const float *x = nullptr;
+            long long t = -1, env = 0;
+            if (lr < rows) {
+                t = lr / nenv;
+                env = e0 + (lr - t * nenv);
+                x = t == 0 ? g.obs0 + env * E : g.obs + ((t - 1) * N + env) * E;
+            }
+            row_x[tid] = x;
+            row_env[tid] = env;
+            row_t[tid] = t;
+        }
+        float acc[4][4] = {};
+        for (int c0 = 0; c0 < Epad; c0 += CHUNK) {
+            const int kc = min(CHUNK, Epad - c0);
+            __syncthreads();
+            load_x(c0);
+            for (int idx = tid; idx < HID * kc; idx += THREADS) {
+                const int j = idx / kc, k = idx - j * kc, e = c0 + k;
+                W1s[j * LD + k] = e < E ? W1[(long long)j * E + e] : 0.0f;
+            }
+            __syncthreads();
+            gemm_nt(Xs, W1s, kc, tr, tj, acc);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float z = acc[i][j] + b1s[tj + 16 * j];
+                H1s[(4 * tr + i) * LD + tj + 16 * j] = z > 0.0f ? z : 0.0f;
+                acc[i][j] = 0.0f;
+            }
+        __syncthreads();
+        gemm_nt(H1s, W2s, HID, tr, tj, acc);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float z = acc[i][j] + b2s[tj + 16 * j];
+                H2s[(4 * tr + i) * LD + tj + 16 * j] = z > 0.0f ? z : 0.0f;
+            }
+        __syncthreads();
+    };
+
+    // ---------------------------------------------------------------- pass 1: probabilities and values of every row
+    for (long long tile = 0; tile < ntiles; ++tile) {
+        forward(tile);
+        {
+            const float *h = H2s + lane * LD;
+            float s = 0.0f, sv = 0.0f;
+#pragma unroll
+            for (int q = 0; q < HID; q += 4) {
+                const float4 x = *reinterpret_cast<const float4 *>(h + q);
+                const float4 w = *reinterpret_cast<const float4 *>(Wps + part * HID + q);
+                s = fmaf(x.x, w.x, s);
+                s = fmaf(x.y, w.y, s);
+                s = fmaf(x.z, w.z, s);
+                s = fmaf(x.w, w.w, s);
+                if (part == 0) {
+                    const float4 u = *reinterpret_cast<const float4 *>(Wvs + q);
+                    sv = fmaf(x.x, u.x, sv);
+                    sv = fmaf(x.y, u.y, sv);
+                    sv = fmaf(x.z, u.z, sv);
+                    sv = fmaf(x.w, u.w, sv);
+                }
+            }
+            zs[lane * 8 + part] = s + bhs[part];
+            if (part == 0) zs[lane * 8 + 4] = sv + bhs[4];
+        }
+        __syncthreads();
+        if (tid < TILE && row_t[tid] >= 0) {
+            const float z0 = zs[tid * 8], z1 = zs[tid * 8 + 1], z2 = zs[tid * 8 + 2], z3 = zs[tid * 8 + 3];
+            const float v = zs[tid * 8 + 4];
+            const float m = fmaxf(fmaxf(z0, z1), fmaxf(z2, z3));
+            const float x0 = expf(z0 - m), x1 = expf(z1 - m), x2 = expf(z2 - m), x3 = expf(z3 - m);
+            const float sum = ((x0 + x1) + x2) + x3;
+            float *o = parked + (tile * TILE + tid) * ROW_FLOATS;
+            *reinterpret_cast<float4 *>(o) = make_float4(x0 / sum, x1 / sum, x2 / sum, x3 / sum);
+            o[4] = v;
+            if (g.values_out != nullptr && row_t[tid] < T) g.values_out[row_t[tid] * N + row_env[tid]] = v;
+        }
+    }
+    __threadfence_block();
+    __syncthreads();
+
+    // ---------------------------------------------------------------- return scan (rl.hip: a2c_returns_kernel, n-step)
+    for (long long i = tid; i < nenv; i += THREADS) {
+        const long long env = e0 + i;
+        float R = parked[(T * nenv + i) * ROW_FLOATS + 4] * (g.dones[(T - 1) * N + env] ? 0.0f : 1.0f);
+        for (long long t = T - 1; t >= 0; --t) {
+            const float nd = g.dones[t * N + env] ? 0.0f : 1.0f;
+            R = g.rewards[t * N + env] + g.gamma * R * nd;
+            parked[(t * nenv + i) * ROW_FLOATS + 5] = R;
+        }
+    }
+    __threadfence_block();
+    __syncthreads();
+
+    // ---------------------------------------------------------------- pass 2: derivatives and weight gradients
+    float gW2[4][4] = {};            // dW2[4 tr + i][4 tj + j]
+    float gWp = 0.0f, gWv = 0.0f;    // dWp[part][lane]; dWv[lane] (part 0)
+    // The bias gradients and the loss sums are plain sums of signed per-row terms that largely cancel (dbv is one number:
+    // sum of (v - R) / B), so a sequential fp32 sum loses what torch's pairwise reductions keep: they run in double.
+    double gb = 0.0;                 // part 1: db2[lane]; part 2: db1[lane]; part 3, lane < 5: dbp / dbv
+    double lv = 0.0, lp = 0.0, le = 0.0; // loss sums (thread 0)
+    const float eps32 = 1.1920928955078125e-07f, hi32 = 1.0f - eps32;
+
+    for (long long tile = 0; tile < ntiles; ++tile) {
+        if (ntiles > 1) forward(tile);
+        if (tid < TILE) {
+            float d[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            float rv = 0.0f, rp = 0.0f, re = 0.0f;
+            const long long t = row_t[tid];
+            if (t >= 0 && t < T) {
+                const float *o = parked + (tile * TILE + tid) * ROW_FLOATS;
+                const float p[4] = {o[0], o[1], o[2], o[3]};
+                const float v = o[4], R = o[5];
+                long long a = g.actions[t * N + row_env[tid]];
+                a = a < 0 ? 0 : (a > 3 ? 3 : a);
+                const float dl = v - R, adv = R - v;
+                float dv;
+                if (g.loss_kind == 0) { // smooth_l1, beta = 1
+                    const float ad = fabsf(dl);
+                    rv = ad < 1.0f ? 0.5f * dl * dl : ad - 0.5f;
+                    dv = ad < 1.0f ? dl : (dl > 0.0f ? 1.0f : -1.0f);
+                } else { // squared error
+                    rv = dl * dl;
+                    dv = 2.0f * dl;
+                }
+                float gk[4], dot = 0.0f;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const bool inside = p[k] > eps32 && p[k] < hi32; // the clamp passes gradient strictly inside only
+                    const float lg = logf(fminf(fmaxf(p[k], eps32), hi32));
+                    re -= p[k] * lg;
+                    gk[k] = g.entropy_coef * (lg + (inside ? 1.0f : 0.0f));
+                    if (k == (int)a) {
+                        rp = -(adv * lg);
+                        if (inside) gk[k] -= adv / p[k];
+                    }
+                    dot = fmaf(gk[k], p[k], dot);
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) d[k] = p[k] * (gk[k] - dot) * g.inv_B;
+                d[4] = dv * g.inv_B;
+            }
+#pragma unroll
+            for (int k = 0; k < 5; ++k) zs[tid * 8 + k] = d[k];
+            lv += (double)wave_sum_f32(rv);
+            lp += (double)wave_sum_f32(rp);
+            le += (double)wave_sum_f32(re);
+        }
+        __syncthreads();
+        // head gradients: sums over the tile's rows, in row order
+        for (int r = 0; r < TILE; ++r) {
+            const float h = H2s[r * LD + lane];
+            gWp = fmaf(zs[r * 8 + part], h, gWp);
+            if (part == 0) gWv = fmaf(zs[r * 8 + 4], h, gWv);
+            if (part == 3 && lane < 5) gb += (double)zs[r * 8 + lane];
+        }
+        // dZ2[r][k] = (sum_a dz[r][a] Wp[a][k] + dv[r] Wv[k]) where unit k of layer 2 is live
+        {
+            const float w0 = Wps[lane], w1 = Wps[HID + lane], w2 = Wps[2 * HID + lane], w3 = Wps[3 * HID + lane];
+            const float wv = Wvs[lane];
+#pragma unroll 4
+            for (int r = part; r < TILE; r += 4) {
+                float s = zs[r * 8] * w0;
+                s = fmaf(zs[r * 8 + 1], w1, s);
+                s = fmaf(zs[r * 8 + 2], w2, s);
+                s = fmaf(zs[r * 8 + 3], w3, s);
+                s = fmaf(zs[r * 8 + 4], wv, s);
+                dZ2s[r * LD + lane] = H2s[r * LD + lane] > 0.0f ? s : 0.0f;
+            }
+        }
+        __syncthreads();
+        if (part == 1)
+            for (int r = 0; r < TILE; ++r) gb += (double)dZ2s[r * LD + lane];
+        gemm_tn(dZ2s, H1s, tr, tj, gW2);
+        {
+            float acc[4][4] = {};
+            gemm_nt(dZ2s, W2Ts, HID, tr, tj, acc);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int o = (4 * tr + i) * LD + tj + 16 * j;
+                    dZ1s[o] = H1s[o] > 0.0f ? acc[i][j] : 0.0f;
+                }
+        }
+        __syncthreads();
+        if (part == 2)
+            for (int r = 0; r < TILE; ++r) gb += (double)dZ1s[r * LD + lane];
+        for (int c0 = 0; c0 < Epad; c0 += CHUNK) {
+            if (xs_c0 != c0) { // (the forward pass of this tile left its last chunk behind)
+                __syncthreads();
+                load_x(c0);
+                __syncthreads();
+            }
+            float acc[4][4] = {};
+            gemm_tn(dZ1s, Xs, tr, tj, acc);
+            if (c0 + 4 * tj < Epad) // (the partial has Epad columns; up to there padded columns hold exact zeros)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    float4 *o = reinterpret_cast<float4 *>(partial + (4 * tr + i) * Epad + c0 + 4 * tj);
+                    float4 v = make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]);
+                    if (tile != 0) {
+                        const float4 old = *o;
+                        v = make_float4(old.x + v.x, old.y + v.y, old.z + v.z, old.w + v.w);
+                    }
+                    *o = v;
+                }
+        }
+        if (ntiles > 1) xs_c0 = -1; // the next tile has other rows
+    }
+
+    float *o = partial + 64 * Epad;
+    if (part == 2) o[lane] = (float)gb; // b1
+    o += 64;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        *reinterpret_cast<float4 *>(o + (4 * tr + i) * HID + 4 * tj) =
+            make_float4(gW2[i][0], gW2[i][1], gW2[i][2], gW2[i][3]);
+    o += 4096;
+    if (part == 1) o[lane] = (float)gb; // b2
+    o += 64;
+    o[part * HID + lane] = gWp;
+    o += 256;
+    if (part == 3 && lane < 4) o[lane] = (float)gb; // bp
+    o += 4;
+    if (part == 0) o[lane] = gWv;
+    o += 64;
+    if (part == 3 && lane == 4) o[0] = (float)gb; // bv
+    o += 1;
+    if (tid == 0) {
+        o[0] = (float)lv;
+        o[1] = (float)lp;
+        o[2] = (float)le;
+    }
+}
+
+// grad[i] = sum over the workgroups, in workgroup order; the three loss sums behind it become means
+__global__ __launch_bounds__(THREADS) void a2c_ff_reduce_kernel(const float *__restrict__ partials, int G, int E,
+                                                                float inv_B, float *__restrict__ grad,
+                                                                float *__restrict__ losses)
+{
+    const long long i = (long long)blockIdx.x * THREADS + threadIdx.x, P = num_params(E), stride = partial_stride(E);
+    if (i >= P + 3) return;
+    const int Epad = padded_inputs(E);
+    const long long src = i < 64LL * E ? (i / E) * Epad + i % E : i - 64LL * E + 64LL * Epad; // dW1 rows are padded
+    double s = 0.0; // (up to 256 signed terms per element: summed in double, rounded once)
+#pragma unroll 8
+    for (int w = 0; w < G; ++w) s += (double)partials[w * stride + src];
+    if (i < P)
+        grad[i] = (float)s;
+    else
+        losses[i - P] = (float)(s * (double)inv_B);
+}
+
+constexpr int APPLY_PER_BLOCK = 4 * THREADS;
+
+// Every workgroup forms sum g^2 over ALL of grad in the same order (so they all hold the same bits), then clips and
+// steps its own 1024 parameters.  step_size = lr / (1 - beta1^step), bc2_sqrt = sqrt(1 - beta2^step), w1 = 1 - beta1 and
+// w2 = 1 - beta2 come from the host, computed in double as torch.optim.Adam does.
+__global__ __launch_bounds__(THREADS) void a2c_ff_apply_kernel(float *__restrict__ params,
+                                                               const float *__restrict__ grad,
+                                                               float *__restrict__ exp_avg,
+                                                               float *__restrict__ exp_avg_sq,
+                                                               float *__restrict__ grad_norm, float step_size,
+                                                               float bc2_sqrt, float beta2, float w1, float w2,
+                                                               float eps, float max_norm, long long P)
+{
+    __shared__ float red[THREADS];
+    const int tid = (int)threadIdx.x;
+    float s = 0.0f;
+    for (long long i = tid; i < P; i += THREADS) s = fmaf(grad[i], grad[i], s);
+    red[tid] = s;
+    __syncthreads();
+    for (int w = THREADS / 2; w >= 1; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    const float norm = sqrtf(red[0]);
+    if (blockIdx.x == 0 && tid == 0 && grad_norm != nullptr) grad_norm[0] = norm;
+    float scale = 1.0f;
+    if (max_norm > 0.0f) scale = fminf(max_norm / (norm + 1e-6f), 1.0f);
+    const long long base = (long long)blockIdx.x * APPLY_PER_BLOCK;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const long long i = base + q * THREADS + tid;
+        if (i < P) {
+            const float gi = grad[i] * scale;
+            const float m = exp_avg[i] + w1 * (gi - exp_avg[i]);
+            const float u = beta2 * exp_avg_sq[i] + w2 * gi * gi;
+            exp_avg[i] = m;
+            exp_avg_sq[i] = u;
+            params[i] = params[i] - step_size * (m / (sqrtf(u) / bc2_sqrt + eps));
+        }
+    }
+}
+
+} // namespace a2c
+} // namespace wurm

@@ -64,7 +64,8 @@ const char *wurm_version(void);
  * changes results, only which kernel serves a call.  set / reset return WURM_ERR_INVALID_ARG for an unknown name,
  * get returns INT64_MIN.  The knobs are PROCESS-WIDE (every env object and thread sees them); an environment variable that
  * is not a whole decimal number leaves the default in place.  wurm_launch_count is an atomic diagnostic counter,
- * wurm_single_last_route names the calling thread's last launch; neither is state a later call depends on. */
+ * wurm_single_last_route and wurm_multi_last_route name the calling thread's last launch; none is state a later call
+ * depends on. */
 int wurm_set_option(const char *name, int64_t value);
 int64_t wurm_get_option(const char *name);
 int wurm_reset_option(const char *name);
@@ -78,6 +79,14 @@ int64_t wurm_launch_count(void);
  * "lane_rollout", "rollout_s9", "rollout_s9_injected", "rollout_lean", "rollout_generic_partial", "rollout_generic_none".
  * Diagnostic only (bench.py and tests/test_dispatch_table.py name a launch by it); a static string. */
 const char *wurm_single_last_route(void);
+
+/* The same for MultiSnake: the kernel instantiation that served the calling thread's last wurm_multi_* launch, by its row in
+ * the list in wurm_amd/csrc/multi_snake.hip ("step_rng_full_k4_s25", "rollout_two_rng", "rollout_group_8215_rng", "reset_wg",
+ * ...; "none" before the first), followed by how it was driven where one kernel is driven in several ways: "+emit_wave" /
+ * "+emit_group" (the per-call step writing 'full' observations through class codes, WURM_MULTI_GROUP_STEP_WPB), "/tapes"
+ * (recorded outcomes injected).  No geometry.  wurm_multi_resident_flush and wurm_multi_colours do not change it.  Diagnostic
+ * only (tests/test_multi_dispatch_table.py pins the choice by it); the string is the thread's own, valid until its next call. */
+const char *wurm_multi_last_route(void);
 
 /* Number of fp32 elements one env's observation occupies (0 = invalid mode for that env family). */
 int64_t wurm_single_obs_elems(int obs_mode, int obs_n, int size);
@@ -478,7 +487,7 @@ int wurm_multi_step_slot(wurm_multi_call *c, const wurm_multi_slabs *slabs, int6
 
 /* The mirror of wurm_multi_call.resident: per env the 16-bit clock grids of the K bodies, the food grid as bytes and three
  * ints per snake — (2 K + 1) S^2 bytes and change instead of (1 + 2 K) S^2 fp32 read every call
- * (wurm_amd/csrc/multi_snake.hip).  Returns its size in bytes, 0 if it is not offered for this batch (fewer than 2^20
+ * (wurm_amd/csrc/multi_device.hpp).  Returns its size in bytes, 0 if it is not offered for this batch (fewer than 2^20
  * cells num_envs * num_snakes * size^2; WURM_RESIDENT_MIN_ENVS replaces that by a number of envs).  Protocol as for
  * wurm_single_call.resident: wurm_multi_step_packed sets c->resident_valid after a launch that maintained the mirror
  * (not with inject / pre_inject: such a call writes a lazy mirror out first and steps the fp32 state), the caller clears it

@@ -487,7 +487,7 @@ class SimMulti(object):
 
     @staticmethod
     def _reset_cfg(cfgb):
-        """what wurm_multi_reset reads of the configuration: respawn_any and colour_random (multi_snake.hip: reroll_colour,
+        """what wurm_multi_reset reads of the configuration: respawn_any and colour_random (multi_reset.hpp: reroll_colour,
         multi_reset_grid; reference :800-831) — a change of the step dynamics between step and reset does not matter to it"""
         c = _lib.MultiConfig.from_buffer_copy(cfgb)
         return b'%d,%d' % (c.respawn_any, c.colour_random)

@@ -1,4 +1,4 @@
-"""`div255` of wurm_amd/csrc/multi_snake.hip (the pixels of MultiSnake's partial_n observations, reference
+"""`div255` of wurm_amd/csrc/multi_device.hpp (the pixels of MultiSnake's partial_n observations, reference
 wurm/envs/multi_snake.py:194-227 `/ 255`): q = x * fl(1/255); q' = fma(fma(-q, 255, x), fl(1/255), q) is the correctly rounded
 IEEE quotient x / 255 for every integer the fast path takes (0 <= x < 70 000).  Checked here in exact rational arithmetic
 (no GPU): the fused operations are rounded once, from the exact value."""

@@ -1,5 +1,5 @@
 """MultiSnake's per-call step on a resident mirror of foods / heads / bodies (wurm_multi_call.resident; the LDS image of
-the env's grids kept between calls, wurm_amd/csrc/multi_snake.hip): eager and lazy, one env per wave and one env per
+the env's grids kept between calls, wurm_amd/csrc/multi_device.hpp): eager and lazy, one env per wave and one env per
 workgroup, every dynamics configuration of the parity suite.
 
 (a) through the C ABI: the oracle follows [postponed reset,] step over many iterations while foods / heads / bodies are

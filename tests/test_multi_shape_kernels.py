@@ -1,5 +1,5 @@
 """The shape-specialised MultiSnake kernels (round 6: K, S and the crop radius compiled in for the shapes the reference's own
-experiments run — multi_snake.hip: shape_constants) against the generic kernels, bit for bit: same source, two
+experiments run — multi_device.hpp: shape_constants) against the generic kernels, bit for bit: same source, two
 instantiations, switched within one process by WURM_MULTI_SHAPE_KERNELS.  The oracle tests at these shapes
 (tests/test_hip_multi_vs_oracle.py, test_hip_multi_fused.py, test_multi_resident.py, test_multi_group_rollout.py,
 test_full_size_parity.py) run the specialised kernels — the default — so together: specialised == oracle == generic.

@@ -496,7 +496,7 @@ def fuzz_grid_lane(rng):
     return desc
 
 
-# (round 6) the shapes with kernels of their own — K, S and the crop radius compiled in (multi_snake.hip: shape_constants)
+# (round 6) the shapes with kernels of their own — K, S and the crop radius compiled in (multi_device.hpp: shape_constants)
 SPECIAL_SHAPES = [(4, 25, 'partial_5'), (4, 25, 'full'), (10, 36, 'full'), (2, 12, 'full')]
 
 

@@ -1020,4 +1020,19 @@ __device__ __forceinline__ int keep_in_lane(int v, int value, u64 lanes)
     return v;
 }
 
+// v = value in lane `dst`, unchanged elsewhere; value and dst wave-uniform.  v_writelane_b32 with the lane select in m0:
+// two ordinary SGPR operands break the constant-bus limit.  (m0 written by the SALU needs no wait state before a lane
+// select; only an SGPR written by the VALU does.)
+__device__ __forceinline__ int set_lane(int v, int value, int dst)
+{
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm" // m0 is reserved, and is named as clobbered on purpose
+    asm("s_mov_b32 m0, %2\n\tv_writelane_b32 %0, %1, m0" : "+v"(v) : "s"(value), "s"(dst) : "m0");
+#pragma clang diagnostic pop
+    return v;
+}
+
+// bit (i & 63) of m, for a branch: s_bitcmp1_b64 reads bits [5:0] of its index operand
+__device__ __forceinline__ bool bit_set(u64 m, int i) { return ((m >> (i & 63)) & 1) != 0; }
+
 } // namespace wurm

@@ -244,8 +244,9 @@ __global__ __launch_bounds__(256) void rollout_lean_kernel(StepArgs p)
 
         for (int j = 0; j < nt; ++j) {
             // ---- step (single_snake.py:197-304; same line references as step_core / fast_step)
-            const int m01 = lane_value(my_mov01, j), m23 = lane_value(my_mov23, j);
-            const int ent = ((o16 & 32) ? m23 : m01) >> (o16 & 16);
+            // the two words are the halves of one 64-bit table: entry o is bits [16 o, 16 o + 16)
+            const u64 mov = (u64)(u32)lane_value(my_mov01, j) | ((u64)(u32)lane_value(my_mov23, j) << 32);
+            const int ent = (int)(u32)(mov >> o16);
             o16 = ent & 48;
             hy1 += (ent << 24) >> 30;                // the head is off the border ring: the move stays on the grid
             hx1 += (ent << 22) >> 30;
@@ -302,7 +303,7 @@ __global__ __launch_bounds__(256) void rollout_lean_kernel(StepArgs p)
                 asm volatile("global_store_dword %0, %1, %2" : : "v"(off_b), "v"(vb), "s"(obs_t) : "memory");
                 obs_t += obs_stride;
             }
-            my_rec = lane == j ? ent : my_rec;
+            my_rec = set_lane(my_rec, ent, j);
 
             // ---- reset of a finished env (single_snake.py:322-387)
             if (__builtin_expect(finished, 0)) {
@@ -389,15 +390,16 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
     const int my_cell = ly * S + lx;
     const u64 RING = ~lane_mask(lane_in);
     int ex = lane_in ? __float2int_rn(envp[2 * S * S + my_cell]) : 0; // expiry clock of the lane's cell (body, re-read)
-    // carried scalars: head code, length, orientation * 16, food code (-1: none), G = clock + length
-    int c = uniform(f.hy) * 8 + uniform(f.hx), L = uniform(f.L), o16 = uniform(f.o) << 4;
+    // carried scalars: head code, orientation * 16, food code (-1: none), the clock T and G = T + length (the length
+    // itself is only ever needed as G - T)
+    int c = uniform(f.hy) * 8 + uniform(f.hx), o16 = uniform(f.o) << 4;
     int foodc = -1;
     if (f.food >= 0) {
         const int fy = uniform(div_size(f.food, g.rcpS)); // (float arithmetic: a VALU result, back to an SGPR)
         foodc = fy * 8 + (uniform(f.food) - fy * S);
     }
     u64 XF = RING | (foodc >= 0 ? 1ull << foodc : 0); // ring + food: the non-body cells that make a step eventful
-    int G = L;
+    int G = uniform(f.L), T = 0;
 
     // partial_n crop: lane owns window cell w (lanes past the window repeat its last cell: same address, same value)
     const int n = OBSK == WURM_OBS_PARTIAL ? p.obs_n : 0, W = 2 * n + 1, W2 = W * W;
@@ -467,23 +469,25 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
         // what lane j keeps of step t0 + j: its move entry, whether it ate, self collision | edge collision << 1
         int my_rec = 0, my_ate = 0, my_fl = 0;
         {   // re-base the clocks so that they cannot overflow however long the tape is
-            const int T = G - L;
             ex = max(ex - T, 0);
-            G = L;
+            G -= T;
+            T = 0;
         }
 
         for (int j = 0; j < nt; ++j) {
-            const u64 lane_j = 1ull << j; // lane j keeps the record of step t0 + j
             // ---- step (single_snake.py:197-304; same line references as step_core / fast_step)
-            const int m01 = lane_value(my_mov01, j), m23 = lane_value(my_mov23, j);
-            const int ent = ((o16 & 32) ? m23 : m01) >> (o16 & 16);
+            // the two words are the halves of one 64-bit table: entry o is bits [16 o, 16 o + 16)
+            const u64 mov = (u64)(u32)lane_value(my_mov01, j) | ((u64)(u32)lane_value(my_mov23, j) << 32);
+            const int ent = (int)(u32)(mov >> o16);
+            my_rec = set_lane(my_rec, ent, j);       // lane j keeps the record of step t0 + j
             o16 = ent & 48;
-            c += (ent << 20) >> 26;                  // the head is inside the ring: the move stays on the grid
+            // c += code step: the head is inside the ring, so the move stays on the grid (in place: left to the compiler, the
+            // sum lands in a new register and the plain move pays a copy on the back edge)
+            asm("s_add_i32 %0, %0, %1" : "+s"(c) : "s"((ent << 20) >> 26) : "scc");
             G += 1;
-            int ate; // head == food (:242; spelled out: the compiler detours through a 64-bit lane mask)
-            asm("s_cmp_eq_u32 %1, %2\n\ts_cselect_b32 %0, 1, 0" : "=s"(ate) : "s"(c), "s"(foodc) : "scc");
-            L += ate;
-            const int T = G - L;                     // :246-249: the clock stands still on the step that eats
+            // T += head != food, through the carry: the clock stands still on the step that eats (:242, :246-249), which
+            // is the length growing by one
+            asm("s_cmp_lg_u32 %1, %2\n\ts_addc_u32 %0, %0, 0" : "+s"(T) : "s"(c), "s"(foodc) : "scc");
             const u64 body = lane_mask(ex > T);      // after the decay, before the head is written
             const u64 head = 1ull << (c & 63);
             ex = keep_in_lane(ex, G, head);          // :258-262 (a head on the ring may land in a wrong lane: it is reset below)
@@ -500,9 +504,12 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
             }
 
             // One test for everything that is not a plain move: the head entered a body cell (:252), the border ring
-            // (:290-295) or the food cell (:242).
-            int event = 0; // 1: self collision, 2: edge collision
+            // (:290-295) or the food cell (:242).  All of it — the reset too — sits behind this one branch, so the plain
+            // move carries no event flag and no second test; the crop below is of the state BEFORE the reset and takes
+            // what it shows (inside, code, mask, shown_food) from there.
+            int shown_food = foodc;
             if (__builtin_expect((((body | XF) >> (c & 63)) & 1) != 0, 0)) {
+                const u64 lane_j = 1ull << (j & 63);
                 if (c == foodc) {                    // :270-282: K-th free interior cell in row-major order
                     my_ate = keep_in_lane(my_ate, 1, lane_j);
                     if constexpr (INJ) {
@@ -518,7 +525,8 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
                     }
                     XF = RING | (foodc >= 0 ? 1ull << foodc : 0);
                 }
-                event = ((RING >> (c & 63)) & 1) ? 2 : ((body >> (c & 63)) & 1) ? 1 : 0;
+                shown_food = foodc;
+                const int event = ((RING >> (c & 63)) & 1) ? 2 : ((body >> (c & 63)) & 1) ? 1 : 0; // self / edge collision
                 if (OBSK == WURM_OBS_PARTIAL && event == 2) {
                     // the head is on the ring and its code may have wrapped: row / column arithmetic from the cell it left
                     const int ai = ent & 3, pc = c - ((ent << 20) >> 26);
@@ -526,6 +534,18 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
                     inside = max((unsigned)(hy + dy0 - 1), (unsigned)(hx + dx0 - 1)) < 7u ? 1u : 0u;
                     code = (hy + dy0) * 8 + hx + dx0;
                     mask = body;
+                }
+                // ---- reset of a finished env (single_snake.py:322-387)
+                if (event != 0) {
+                    my_fl = keep_in_lane(my_fl, event, lane_j);
+                    const int ra = lane_value(my_reset.a, j), rb = lane_value(my_reset.b, j);
+                    o16 = (ra & 3) << 4;
+                    foodc = ra >> 2;
+                    XF = INJ ? (RING | (foodc >= 0 ? 1ull << foodc : 0)) : (RING | (1ull << foodc));
+                    c = rb & 127;
+                    const int sc = (rb >> 7) & 127, tc = rb >> 14;
+                    ex = lane == tc ? T + 1 : 0; ex = lane == sc ? T + 2 : ex; ex = lane == c ? T + 3 : ex;
+                    G = T + 3;                       // length 3
                 }
             }
 
@@ -551,28 +571,13 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
                     "v_cndmask_b32_e64 %1, 0, %0, %4\n\t"
                     "v_cndmask_b32_e64 %2, %1, %11, %5"
                     : "=&v"(vr), "=&v"(vb), "=&v"(vg), "=&s"(m_free), "=&s"(m_not_food), "=&s"(m_taken)
-                    : "v"(inside), "v"(taken), "s"(foodc), "v"(code), "v"(both), "v"(green));
+                    : "v"(inside), "v"(taken), "s"(shown_food), "v"(code), "v"(both), "v"(green));
                 // scalar base + 32-bit lane offset form, spelled out: the compiler hoists the zero-extension of the
                 // lane offsets out of the loop and then pays a 64-bit VALU add per store.  (Untracked stores are
                 // harmless for its vmcnt bookkeeping: nothing is read back and waits only become conservative.)
                 asm volatile("global_store_dword %0, %1, %6\n\tglobal_store_dword %2, %3, %6\n\tglobal_store_dword %4, %5, %6"
                              : : "v"(off_r), "v"(vr), "v"(off_g), "v"(vg), "v"(off_b), "v"(vb), "s"(obs_t) : "memory");
                 obs_t += obs_stride;
-            }
-            my_rec = keep_in_lane(my_rec, ent, lane_j);
-
-            // ---- reset of a finished env (single_snake.py:322-387)
-            if (__builtin_expect(event != 0, 0)) {
-                my_fl = keep_in_lane(my_fl, event, lane_j);
-                const int ra = lane_value(my_reset.a, j), rb = lane_value(my_reset.b, j);
-                o16 = (ra & 3) << 4;
-                foodc = ra >> 2;
-                XF = INJ ? (RING | (foodc >= 0 ? 1ull << foodc : 0)) : (RING | (1ull << foodc));
-                c = rb & 127;
-                const int sc = (rb >> 7) & 127, tc = rb >> 14;
-                ex = lane == tc ? T + 1 : 0; ex = lane == sc ? T + 2 : ex; ex = lane == c ? T + 3 : ex;
-                L = 3;
-                G = T + 3;
             }
         }
         if (lane < nt) {
@@ -585,7 +590,6 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
         }
     }
     if (lane_in) { // the ring was empty and still is
-        const int T = G - L;
         envp[my_cell] = lane == foodc ? 1.0f : 0.0f;
         envp[S * S + my_cell] = lane == c ? 1.0f : 0.0f;
         envp[2 * S * S + my_cell] = (float)max(ex - T, 0);

@@ -3,9 +3,11 @@
 half is `env.policy_rollout(learner.params, state, update_steps)` (policy -> sample -> step -> reset inside the env
 kernel, as in examples/a2c_fused_actor.py), the learning half is `learner.update(state, out)`: forward, return scan, loss,
 backward pass, clip_grad_norm_ and Adam in three launches (wurm_amd.rl.FusedA2CLearner).  Per update the host issues four
-kernel launches and reads nothing back; the loss is copied to the host only for a log line.
+kernel launches and reads nothing back; the loss is copied to the host only for a log line.  `--gae-lambda` switches the
+returns from n-step to generalised advantage estimation (the reference's `--gae-lambda`), still in the same launches.
 
     python examples/a2c_fused_learner.py --num-envs 512 --steps 20000
+    python examples/a2c_fused_learner.py --num-envs 512 --steps 20000 --gae-lambda 0.95
 """
 import argparse
 import os
@@ -21,12 +23,13 @@ from wurm_amd.rl import FusedA2CLearner  # noqa: E402
 
 
 def run(num_envs=512, size=9, observation='partial_2', steps=20000, update_steps=5, gamma=0.99, lr=1e-3, entropy=0.01,
-        log_interval=2000, seed=0, device='cuda', verbose=True):
+        log_interval=2000, seed=0, device='cuda', verbose=True, gae_lambda=None):
     torch.manual_seed(seed)
     env = SingleSnake(num_envs=num_envs, size=size, observation_mode=observation, device=device, seed=seed)
     state = env.reset()                                                     # main.py:195
     model = FeedforwardAgent(num_actions=4, num_layers=2, hidden_units=64, num_inputs=state[0].numel()).to(device)
-    learner = FusedA2CLearner(model, lr=lr, gamma=gamma, entropy_coef=entropy, max_grad_norm=0.5)
+    learner = FusedA2CLearner(model, lr=lr, gamma=gamma, entropy_coef=entropy, max_grad_norm=0.5,
+                              use_gae=gae_lambda is not None, gae_lambda=gae_lambda)        # multiagent.py:274-275
     totals = torch.zeros(2, dtype=torch.float64, device=device)             # rewards, dones since the last log line
     history, t0, last = [], time.perf_counter(), 0
     for i_step in range(update_steps, steps + 1, update_steps):
@@ -56,5 +59,7 @@ if __name__ == '__main__':
     ap.add_argument('--steps', type=int, default=20000)
     ap.add_argument('--update-steps', type=int, default=5)
     ap.add_argument('--lr', type=float, default=1e-3)
+    ap.add_argument('--gae-lambda', type=float, default=None, help='GAE with this lambda instead of n-step returns')
     args = ap.parse_args()
-    run(args.num_envs, args.size, args.observation, args.steps, args.update_steps, lr=args.lr)
+    run(args.num_envs, args.size, args.observation, args.steps, args.update_steps, lr=args.lr,
+        gae_lambda=args.gae_lambda)

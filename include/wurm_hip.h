@@ -588,7 +588,7 @@ int wurm_single_stats(const float *envs, const float *reward, const uint8_t *don
 
 /* ------------------------------------------------------------------------------------------- fused A2C learner
  * One update of the 2 x 64 feed-forward actor-critic (wurm_amd/agents.py) from the outputs of a policy rollout:
- * batched forward, the n-step return scan of wurm_a2c_returns (use_gae = 0), the loss of experiments/main.py:236-242
+ * batched forward, the return scan of wurm_a2c_returns (n-step, or GAE through the _gae entry points), the loss of experiments/main.py:236-242
  * with A2C(gamma) defaults, its gradient, clip_grad_norm_ and torch.optim.Adam — three launches, no host
  * synchronisation, no atomics (bit-identical from run to run).  Kernels: wurm_amd/csrc/a2c_learner.hpp.
  *   params (P) as pack_policy_params, P = 64 E + 64 + 4096 + 64 + 256 + 4 + 64 + 1;  obs0 (N,E) the input of step 0;
@@ -632,6 +632,33 @@ int wurm_a2c_ff_update(float *params, const float *obs0, const float *obs, const
                        int64_t workspace_bytes, int64_t num_envs, int64_t num_steps, int num_inputs, float *exp_avg,
                        float *exp_avg_sq, float *grad_norm, int64_t step, float lr, float beta1, float beta2, float eps,
                        float max_grad_norm, void *stream);
+
+/* The same two calls with generalised advantage estimation (A2C(gamma, use_gae=True, gae_lambda), wurm/rl/a2c.py:50-59):
+ * the same three launches and workspace, the arguments of wurm_a2c_ff_grad / _update followed by
+ *   gamma_lambda: (float)(gamma * gae_lambda), the product rounded by the caller as for wurm_a2c_returns; finite and
+ *                 >= 0, anything else is WURM_ERR_INVALID_ARG;
+ *   returns_out:  nullable, (T,N): R, bit for bit what wurm_a2c_returns(use_gae = 1) makes of values_out and the value of
+ *                 obs[T-1].
+ *   delta_t = r_t + gamma * v_{t+1} * !done_t - v_t (v_T: the value of obs[T-1]);  gae_t = delta_t + gamma_lambda *
+ *   !done_t * gae_{t+1};  R_t = gae_t + v_t.  The loss is the one above with this R; R - v in the policy term is still a
+ *   constant, but R in the value term is NOT (the reference does not detach it): with G_t = -l'(v_t - R_t) / (N T) and
+ *   A_t = G_t + gamma_lambda * !done_{t-1} * A_{t-1} (the adjoint of wurm_a2c_returns_backward),
+ *   dloss/dv_t = l'(v_t - R_t) / (N T) + G_t - A_t + gamma * !done_{t-1} * A_{t-1}.  v_T carries no gradient
+ *   (experiments/main.py:233-234 computes it under no_grad).  At gae_lambda = 1 the added term vanishes and R is the
+ *   n-step return, to rounding. */
+int wurm_a2c_ff_grad_gae(const float *params, const float *obs0, const float *obs, const int64_t *actions,
+                         const float *rewards, const uint8_t *dones, float gamma, float entropy_coef,
+                         int value_loss_kind, float *grad, float *losses, float *values_out, void *workspace,
+                         int64_t workspace_bytes, int64_t num_envs, int64_t num_steps, int num_inputs, void *stream,
+                         float gamma_lambda, float *returns_out);
+
+int wurm_a2c_ff_update_gae(float *params, const float *obs0, const float *obs, const int64_t *actions,
+                           const float *rewards, const uint8_t *dones, float gamma, float entropy_coef,
+                           int value_loss_kind, float *grad, float *losses, float *values_out, void *workspace,
+                           int64_t workspace_bytes, int64_t num_envs, int64_t num_steps, int num_inputs,
+                           float *exp_avg, float *exp_avg_sq, float *grad_norm, int64_t step, float lr, float beta1,
+                           float beta2, float eps, float max_grad_norm, void *stream, float gamma_lambda,
+                           float *returns_out);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,7 @@ measurement, appended to profiles/r08_a2c_learner.jsonl (or --out).  Needs the G
 
     tools/bench_a2c_learner.py                 # update times and end-to-end rates
     tools/bench_a2c_learner.py --trace-only    # a few fused updates only: the target of rocprofv3 --kernel-trace --stats
+    tools/bench_a2c_learner.py --gae-lambda 0.95   # both learners with GAE returns (rows carry "gae_lambda")
 """
 import argparse
 import json
@@ -78,13 +79,15 @@ def main():
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'r08_a2c_learner.jsonl'))
     ap.add_argument('--trace-only', action='store_true')
     ap.add_argument('--skip-end-to-end', action='store_true')
+    ap.add_argument('--gae-lambda', type=float, default=None, help='GAE returns with this lambda in both learners')
     args = ap.parse_args()
+    gae = dict(use_gae=args.gae_lambda is not None, gae_lambda=args.gae_lambda)
     assert torch.cuda.is_available(), 'this benchmark needs the GPU'
     dev = torch.device('cuda', 0)
     rows = []
     if args.trace_only:
         state, out = window(512, 5, 75, dev)
-        learner = FusedA2CLearner(FeedforwardAgent(4, 2, 64, 75).to(dev), entropy_coef=0.01)
+        learner = FusedA2CLearner(FeedforwardAgent(4, 2, 64, 75).to(dev), entropy_coef=0.01, **gae)
         before = _lib.lib().wurm_launch_count()
         for _ in range(20):
             learner.update(state, out)
@@ -95,9 +98,9 @@ def main():
     for N, T, E in SHAPES:
         state, out = window(N, T, E, dev)
         torch.manual_seed(0)
-        learner = FusedA2CLearner(FeedforwardAgent(4, 2, 64, E).to(dev), entropy_coef=0.01)
+        learner = FusedA2CLearner(FeedforwardAgent(4, 2, 64, E).to(dev), entropy_coef=0.01, **gae)
         model = FeedforwardAgent(4, 2, 64, E).to(dev)
-        optimizer, a2c = torch.optim.Adam(model.parameters(), lr=1e-3), A2C(gamma=0.99)
+        optimizer, a2c = torch.optim.Adam(model.parameters(), lr=1e-3), A2C(gamma=0.99, **gae)
         fused = lambda: learner.update(state, out)
         eager = lambda: torch_update(model, optimizer, a2c, state, out)
         for _ in range(20):
@@ -108,7 +111,8 @@ def main():
         for _ in range(2):  # alternate the two learners
             for name, fn in (('fused', fused), ('torch', eager)):
                 res.setdefault(name, []).append(time_ms(fn, reps=7, inner=50))
-        row = {'what': 'update_ms', 'num_envs': N, 'num_steps': T, 'num_inputs': E, 'gflop': flops(N, T, E) / 1e9}
+        row = {'what': 'update_ms', 'num_envs': N, 'num_steps': T, 'num_inputs': E, 'gflop': flops(N, T, E) / 1e9,
+               'gae_lambda': args.gae_lambda}
         for name, r in res.items():
             row[name + '_ms_median'] = statistics.median(x[0] for x in r)
             row[name + '_ms_min'] = min(x[1] for x in r)
@@ -117,7 +121,7 @@ def main():
         row['fused_gflops'] = row['gflop'] / row['fused_ms_median'] * 1e3
         rows.append(row)
         print(json.dumps(row), flush=True)
-    if not args.skip_end_to_end:
+    if not args.skip_end_to_end and args.gae_lambda is None:  # (examples/a2c_fused_actor.py has n-step returns only)
         import a2c_fused_actor
         import a2c_fused_learner
         for T in (5, 20):

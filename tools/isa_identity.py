@@ -6,8 +6,11 @@ plus `--cuda-device-only -S`; each assembly file is cut into per-symbol bodies (
 apart) and the bodies are compared BY NAME, because the order of emission follows the order of the source.  Local labels
 and the compiler's loop comments carry the function's ordinal (.LBB12_3, BB12_3, .Lfunc_end12), which is dropped first.
 One line per unit: kernels, identical code, identical descriptors, the demangled names of any that differ / come / go.
+A kernel that only changed its NAME (it became the instantiation of a template, say) is compared with its successor when
+told so: --alias BASE_SYMBOL=HEAD_SYMBOL (mangled names; may be repeated) reads the base's assembly with the one name
+written as the other.
 
-usage: tools/isa_identity.py BASE_REV [--jobs N] [--keep DIR [--reuse]] > profiles/rNN_isa_identity.txt    (exit status 1 on a difference)"""
+usage: tools/isa_identity.py BASE_REV [--jobs N] [--keep DIR [--reuse]] [--alias OLD=NEW] > profiles/rNN_isa_identity.txt    (exit status 1 on a difference)"""
 import argparse
 import os
 import re
@@ -27,18 +30,22 @@ def compile_unit(tree, unit, out):
         sys.exit(f'{tree}: {unit}.hip does not compile\n{r.stderr[-4000:]}')
 
 
-def symbols(path):
-    """{name: (code, descriptor or None)} for every function of an assembly file"""
+def symbols(path, alias=()):
+    """{name: (code, descriptor or None)} for every function of an assembly file; alias: (old, new) symbol names"""
     out, name, code, desc, in_desc = {}, None, [], [], False
     ordinal = re.compile(r'(?<![0-9A-Za-z])(\.LBB|BB|\.Lfunc_end|\.Lfunc_begin|\.Ltmp)\d+')
     for ln in open(path):
         ln = ln.rstrip()
+        for old, new in alias:
+            ln = re.sub(r'(?<![0-9A-Za-z_])' + re.escape(old) + r'(?![0-9A-Za-z_])', new, ln)
         if ln.startswith('\t.type\t') and ln.endswith(',@function'):
             name, code, desc, in_desc = ln.split('\t')[2][:-len(',@function')], [], [], False
             end = '\t.size\t' + name + ','
             continue
         if name is None:
             continue
+        if ln == '\t.text' or ln.startswith('\t.section\t'):  # where the body is placed (an instantiation of a template
+            continue                                           # has a section of its own) is not part of it
         if 'BB' in ln or '.L' in ln: # (and the comment column, which moves with the ordinal's width)
             ln = re.sub(r'\s+;', ' ;', ordinal.sub(r'\1', ln))
         if ln.startswith('\t.amdhsa_kernel'):
@@ -58,7 +65,10 @@ def main():
     ap.add_argument('--jobs', type=int, default=8)
     ap.add_argument('--keep', help='directory that keeps the assembly files (base/, head/)')
     ap.add_argument('--reuse', action='store_true', help='compare the assembly files --keep already holds, compile nothing')
+    ap.add_argument('--alias', action='append', default=[], metavar='OLD=NEW',
+                    help='a symbol of the base that the working tree has under another (mangled) name')
     a = ap.parse_args()
+    alias = [tuple(x.split('=', 1)) for x in a.alias]
     work = a.keep or tempfile.mkdtemp(prefix='isa_identity_')
     base_tree = os.path.join(work, 'base_tree')
     for d in ('base', 'head', 'base_tree'):
@@ -73,12 +83,14 @@ def main():
             list(ex.map(lambda j: compile_unit(*j), jobs))
     rev = subprocess.run(['git', '-C', ROOT, 'rev-parse', '--short', a.base], capture_output=True, text=True).stdout.strip()
     print(f'# device assembly of the working tree against {rev}: hipcc --offload-arch=gfx950 {" ".join(FLAGS)}')
+    for old, new in alias:
+        print(f'# base symbol {old} is compared as {new}')
     print(f'# {"unit":18s} {"kernels":>8s} {"same code":>10s} {"same descr":>11s}  differing / added / removed symbols')
     same = units(base_tree) == units(ROOT)
     if not same:
         print(f'# translation units differ: {units(base_tree)} -> {units(ROOT)}')
     for u in sorted(set(units(base_tree)) & set(units(ROOT))):
-        b, h = symbols(os.path.join(work, 'base', u + '.s')), symbols(os.path.join(work, 'head', u + '.s'))
+        b, h = symbols(os.path.join(work, 'base', u + '.s'), alias), symbols(os.path.join(work, 'head', u + '.s'))
         kernels = [n for n in h if h[n][1] is not None]
         both = [n for n in kernels if n in b]
         odd = [n for n in both if b[n] != h[n]] + [n for n in set(b) ^ set(h)] + \

@@ -30,7 +30,7 @@ SYMBOLS = [
     'wurm_a2c_returns', 'wurm_a2c_returns_backward', 'wurm_single_stats', 'wurm_single_policy_rollout',
     'wurm_single_policy_rollout_mode', 'wurm_grid_policy_rollout', 'wurm_policy_last_route',
     'wurm_a2c_ff_workspace_bytes', 'wurm_a2c_ff_grad', 'wurm_a2c_ff_apply', 'wurm_a2c_ff_update',
-    'wurm_a2c_ff_hyper_parameter',
+    'wurm_a2c_ff_hyper_parameter', 'wurm_a2c_ff_grad_gae', 'wurm_a2c_ff_update_gae',
 ]
 
 

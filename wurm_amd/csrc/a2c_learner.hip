@@ -66,12 +66,16 @@ int check_apply_args(const float *params, const float *grad, const float *exp_av
     return WURM_OK;
 }
 
+// gamma * lambda as the caller rounded it: finite and not negative (refused like the other arguments, before any launch)
+bool valid_gamma_lambda(float gamma_lambda) { return std::isfinite(gamma_lambda) && gamma_lambda >= 0.0f; }
+
+template <bool GAE>
 void launch_grad(const float *params, const float *obs0, const float *obs, const int64_t *actions,
                  const float *rewards, const uint8_t *dones, float gamma, float entropy_coef, int value_loss_kind,
                  float *grad, float *losses, float *values_out, void *workspace, int64_t N, int64_t T, int E,
-                 hipStream_t stream)
+                 hipStream_t stream, float gamma_lambda = 0.0f, float *returns_out = nullptr)
 {
-    MainArgs a;
+    typename main_args<GAE>::type a;
     a.params = params;
     a.obs0 = obs0;
     a.obs = obs;
@@ -89,7 +93,11 @@ void launch_grad(const float *params, const float *obs0, const float *obs, const
     a.gamma = gamma;
     a.entropy_coef = entropy_coef;
     a.inv_B = 1.0f / (float)(N * T);
-    WURM_LAUNCH(a2c_ff_main_kernel, dim3((unsigned)a.G), dim3(THREADS), 0, stream, a);
+    if constexpr (GAE) {
+        a.gamma_lambda = gamma_lambda;
+        a.returns_out = returns_out;
+    }
+    WURM_LAUNCH(a2c_ff_main_kernel<GAE>, dim3((unsigned)a.G), dim3(THREADS), 0, stream, a);
     const long long P = num_params(E);
     WURM_LAUNCH(a2c_ff_reduce_kernel, dim3((unsigned)((P + 3 + THREADS - 1) / THREADS)), dim3(THREADS), 0, stream,
                 a.partials, a.G, E, a.inv_B, grad, losses);
@@ -125,8 +133,25 @@ int wurm_a2c_ff_grad(const float *params, const float *obs0, const float *obs, c
                                    workspace_bytes, num_envs, num_steps, num_inputs);
     if (rc != WURM_OK) return rc;
     (void)hipGetLastError();
-    launch_grad(params, obs0, obs, actions, rewards, dones, gamma, entropy_coef, value_loss_kind, grad, losses,
-                values_out, workspace, num_envs, num_steps, num_inputs, (hipStream_t)stream);
+    launch_grad<false>(params, obs0, obs, actions, rewards, dones, gamma, entropy_coef, value_loss_kind, grad, losses,
+                       values_out, workspace, num_envs, num_steps, num_inputs, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+}
+
+int wurm_a2c_ff_grad_gae(const float *params, const float *obs0, const float *obs, const int64_t *actions,
+                         const float *rewards, const uint8_t *dones, float gamma, float entropy_coef,
+                         int value_loss_kind, float *grad, float *losses, float *values_out, void *workspace,
+                         int64_t workspace_bytes, int64_t num_envs, int64_t num_steps, int num_inputs, void *stream,
+                         float gamma_lambda, float *returns_out)
+{
+    if (!valid_gamma_lambda(gamma_lambda)) return WURM_ERR_INVALID_ARG;
+    const int rc = check_grad_args(params, obs0, obs, actions, rewards, dones, value_loss_kind, grad, losses, workspace,
+                                   workspace_bytes, num_envs, num_steps, num_inputs);
+    if (rc != WURM_OK) return rc;
+    (void)hipGetLastError();
+    launch_grad<true>(params, obs0, obs, actions, rewards, dones, gamma, entropy_coef, value_loss_kind, grad, losses,
+                      values_out, workspace, num_envs, num_steps, num_inputs, (hipStream_t)stream, gamma_lambda,
+                      returns_out);
     return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
 }
 
@@ -163,8 +188,32 @@ int wurm_a2c_ff_update(float *params, const float *obs0, const float *obs, const
     rc = check_apply_args(params, grad, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, P);
     if (rc != WURM_OK) return rc;
     (void)hipGetLastError();
-    launch_grad(params, obs0, obs, actions, rewards, dones, gamma, entropy_coef, value_loss_kind, grad, losses,
-                values_out, workspace, num_envs, num_steps, num_inputs, (hipStream_t)stream);
+    launch_grad<false>(params, obs0, obs, actions, rewards, dones, gamma, entropy_coef, value_loss_kind, grad, losses,
+                       values_out, workspace, num_envs, num_steps, num_inputs, (hipStream_t)stream);
+    launch_apply(params, grad, exp_avg, exp_avg_sq, grad_norm, step, lr, beta1, beta2, eps, max_grad_norm, P,
+                 (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+}
+
+int wurm_a2c_ff_update_gae(float *params, const float *obs0, const float *obs, const int64_t *actions,
+                           const float *rewards, const uint8_t *dones, float gamma, float entropy_coef,
+                           int value_loss_kind, float *grad, float *losses, float *values_out, void *workspace,
+                           int64_t workspace_bytes, int64_t num_envs, int64_t num_steps, int num_inputs,
+                           float *exp_avg, float *exp_avg_sq, float *grad_norm, int64_t step, float lr, float beta1,
+                           float beta2, float eps, float max_grad_norm, void *stream, float gamma_lambda,
+                           float *returns_out)
+{
+    if (!valid_gamma_lambda(gamma_lambda)) return WURM_ERR_INVALID_ARG;
+    int rc = check_grad_args(params, obs0, obs, actions, rewards, dones, value_loss_kind, grad, losses, workspace,
+                             workspace_bytes, num_envs, num_steps, num_inputs);
+    if (rc != WURM_OK) return rc;
+    const int64_t P = a2c::num_params(num_inputs);
+    rc = check_apply_args(params, grad, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, P);
+    if (rc != WURM_OK) return rc;
+    (void)hipGetLastError();
+    launch_grad<true>(params, obs0, obs, actions, rewards, dones, gamma, entropy_coef, value_loss_kind, grad, losses,
+                      values_out, workspace, num_envs, num_steps, num_inputs, (hipStream_t)stream, gamma_lambda,
+                      returns_out);
     launch_apply(params, grad, exp_avg, exp_avg_sq, grad_norm, step, lr, beta1, beta2, eps, max_grad_norm, P,
                  (hipStream_t)stream);
     return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;

@@ -13,9 +13,12 @@
 // zero-padded to a multiple of 16 on both sides, so a padded product is an exact zero.
 //   pass 1: forward of every tile -> softmax probabilities and value of every row, parked in the workspace
 //           (6 floats per row; written and read by this workgroup only)
-//   scan:   one thread per env walks its T rows backwards (the fp32 expression of rl.hip: a2c_returns_kernel)
+//   scan:   one thread per env walks its T rows backwards (the fp32 expression of rl.hip: a2c_returns_kernel).  The GAE
+//           instantiation (a2c_ff_main_kernel<true>) builds R from the parked values instead and then walks forwards once:
+//           the scan's adjoint (rl.hip: a2c_returns_backward_kernel) turns G = dL/dR into the term `extra` that R's
+//           dependence on v adds to dL/dv, parked beside R
 //   pass 2: forward of the tile again (skipped when the workgroup has a single tile: H1 / H2 are still in LDS), the loss
-//           derivatives per row, then dZ2 = (dz Wp + dv Wv) [H2 > 0], dW2 += dZ2^T H1, dZ1 = (dZ2 W2) [H1 > 0],
+//           derivatives per row (GAE: dv = l'(v - R) + extra), then dZ2 = (dz Wp + dv Wv) [H2 > 0], dW2 += dZ2^T H1, dZ1 = (dZ2 W2) [H1 > 0],
 //           dW1 += dZ1^T X.  dW2, the head and bias gradients accumulate in registers over the tiles; dW1 (up to 128 floats
 //           per thread at E = 507) accumulates in the workgroup's own partial, read and written by the same thread.
 // Rows past the workgroup's last row and the bootstrap rows get dz = dv = 0, so they add exact zeros everywhere.
@@ -32,7 +35,7 @@ constexpr int TILE = 64;     // rows per tile
 constexpr int LD = 68;       // floats between rows of an LDS image
 constexpr int CHUNK = 64;    // inputs per pass through LDS
 constexpr int THREADS = 256;
-constexpr int ROW_FLOATS = 8; // parked per row: p0..p3, v, R (+ 2 unused: 32-byte rows)
+constexpr int ROW_FLOATS = 8; // parked per row: p0..p3, v, R, extra (GAE only) (+ 1 unused: 32-byte rows)
 constexpr int MAX_GROUPS = 256;
 
 __host__ __device__ inline long long num_params(int E) { return 64LL * E + 64 + 4096 + 64 + 256 + 4 + 64 + 1; }
@@ -56,6 +59,15 @@ struct MainArgs {
     int E, G, loss_kind;
     float gamma, entropy_coef, inv_B;
 };
+
+// what the GAE instantiation takes on top (the n-step kernel keeps its argument block as it is)
+struct GaeArgs : MainArgs {
+    float *returns_out; // nullable, (T, N)
+    float gamma_lambda; // (float)(gamma * lambda), rounded by the caller
+};
+
+template <bool GAE> struct main_args { using type = MainArgs; };
+template <> struct main_args<true> { using type = GaeArgs; };
 
 // acc[i][j] += sum_k A[4 tr + i][k] * B[tj + 16 j][k], k < K (a multiple of 4)
 __device__ __forceinline__ void gemm_nt(const float *A, const float *B, int K, int tr, int tj, float (&acc)[4][4])
@@ -104,7 +116,18 @@ __device__ __forceinline__ float wave_sum_f32(float v) // fixed butterfly order:
     return v;
 }
 
-__global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(MainArgs g)
+// d l(x) / dx of the value loss at x = v - R
+__device__ __forceinline__ float value_loss_derivative(int loss_kind, float dl)
+{
+    if (loss_kind == 0) { // smooth_l1, beta = 1
+        const float ad = fabsf(dl);
+        return ad < 1.0f ? dl : (dl > 0.0f ? 1.0f : -1.0f);
+    }
+    return 2.0f * dl; // squared error
+}
+
+template <bool GAE>
+__global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(typename main_args<GAE>::type g)
 {
     __shared__ __attribute__((aligned(16))) float Xs[TILE * LD], W1s[HID * LD], W2s[HID * LD], W2Ts[HID * LD];
     __shared__ __attribute__((aligned(16))) float H1s[TILE * LD], H2s[TILE * LD], dZ2s[TILE * LD], dZ1s[TILE * LD];
@@ -241,14 +264,41 @@ __global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(MainArgs g)
     __threadfence_block();
     __syncthreads();
 
-    // ---------------------------------------------------------------- return scan (rl.hip: a2c_returns_kernel, n-step)
+    // ---------------------------------------------------------------- return scan (rl.hip: a2c_returns_kernel)
     for (long long i = tid; i < nenv; i += THREADS) {
         const long long env = e0 + i;
-        float R = parked[(T * nenv + i) * ROW_FLOATS + 4] * (g.dones[(T - 1) * N + env] ? 0.0f : 1.0f);
-        for (long long t = T - 1; t >= 0; --t) {
-            const float nd = g.dones[t * N + env] ? 0.0f : 1.0f;
-            R = g.rewards[t * N + env] + g.gamma * R * nd;
-            parked[(t * nenv + i) * ROW_FLOATS + 5] = R;
+        if constexpr (GAE) {
+            // backwards: delta_t = r_t + gamma v_{t+1} nd_t - v_t, gae_t = delta_t + gamma_lambda nd_t gae_{t+1}, R = gae + v
+            float gae = 0.0f, next = parked[(T * nenv + i) * ROW_FLOATS + 4];
+            for (long long t = T - 1; t >= 0; --t) {
+                float *o = parked + (t * nenv + i) * ROW_FLOATS;
+                const float nd = g.dones[t * N + env] ? 0.0f : 1.0f, v = o[4];
+                const float delta = g.rewards[t * N + env] + g.gamma * next * nd - v;
+                gae = delta + g.gamma_lambda * nd * gae;
+                const float R = gae + v;
+                o[5] = R;
+                if (g.returns_out != nullptr) g.returns_out[t * N + env] = R;
+                next = v;
+            }
+            // forwards, the adjoint (rl.hip: a2c_returns_backward_kernel) with G_t = dL/dR_t = -l'(v_t - R_t) before the
+            // 1 / B that pass 2 applies: A_t = G_t + gamma_lambda nd_{t-1} A_{t-1} is dL/dgae_t, and v_t enters R_t, delta_t
+            // and delta_{t-1}: extra_t = G_t - A_t + gamma nd_{t-1} A_{t-1}.  The bootstrap value gets no gradient.
+            float A_prev = 0.0f, nd_prev = 0.0f;
+            for (long long t = 0; t < T; ++t) {
+                float *o = parked + (t * nenv + i) * ROW_FLOATS;
+                const float G = -value_loss_derivative(g.loss_kind, o[4] - o[5]);
+                const float A = G + g.gamma_lambda * nd_prev * A_prev;
+                o[6] = G - A + g.gamma * nd_prev * A_prev;
+                A_prev = A;
+                nd_prev = g.dones[t * N + env] ? 0.0f : 1.0f;
+            }
+        } else {
+            float R = parked[(T * nenv + i) * ROW_FLOATS + 4] * (g.dones[(T - 1) * N + env] ? 0.0f : 1.0f);
+            for (long long t = T - 1; t >= 0; --t) {
+                const float nd = g.dones[t * N + env] ? 0.0f : 1.0f;
+                R = g.rewards[t * N + env] + g.gamma * R * nd;
+                parked[(t * nenv + i) * ROW_FLOATS + 5] = R;
+            }
         }
     }
     __threadfence_block();
@@ -285,6 +335,7 @@ __global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(MainArgs g)
                     rv = dl * dl;
                     dv = 2.0f * dl;
                 }
+                if constexpr (GAE) dv += o[6]; // R is a function of the values: what comes back through it
                 float gk[4], dot = 0.0f;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {

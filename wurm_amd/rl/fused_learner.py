@@ -4,11 +4,18 @@ weights, with no host synchronisation (include/wurm_hip.h: wurm_a2c_ff_update; w
 
 The agent's eight parameters are moved into ONE contiguous fp32 buffer in `pack_policy_params` order and become views
 of it, so `learner.params` is directly the `params` argument of `policy_rollout` and the module always shows the
-current weights.  GAE, return normalisation and a custom value loss are not part of the fused path
-(NotImplementedError: keep wurm_amd.rl.A2C and torch for those).
+current weights.
+
+Returns are the n-step ones of A2C(gamma) or, with `use_gae=True, gae_lambda=...`, generalised advantage estimates
+(wurm/rl/a2c.py:50-59) with the gradient that flows through them into the value head, as the reference's undetached
+`returns` have it (wurm_a2c_ff_grad_gae / wurm_a2c_ff_update_gae: the same three launches).  Return normalisation and a
+custom value loss are not part of the fused path (NotImplementedError: keep wurm_amd.rl.A2C and torch for those):
+normalised returns need the mean and the standard deviation of all N T returns between the scan and the backward pass,
+which one workgroup per block of envs cannot know.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from wurm_amd import _lib
@@ -31,14 +38,16 @@ class FusedA2CLearner(object):
         lr, betas, eps: torch.optim.Adam's (no weight decay, no amsgrad)
         gamma: discount;  entropy_coef: weight of the mean entropy;  max_grad_norm: clip_grad_norm_'s (<= 0: none)
         value_loss: 'smooth_l1' (F.smooth_l1_loss, the reference's default) or 'mse'
+        use_gae, gae_lambda: A2C's; `gae_lambda` is required with `use_gae` and ignored without it
     """
 
     def __init__(self, agent: FeedforwardAgent, lr: float = 1e-3, gamma: float = 0.99, entropy_coef: float = 0.0,
                  max_grad_norm: float = 0.5, betas=(0.9, 0.999), eps: float = 1e-8, value_loss: str = 'smooth_l1',
-                 use_gae: bool = False, normalise_returns: bool = False):
-        if use_gae or normalise_returns:
-            raise NotImplementedError('the fused learner computes plain n-step returns: use wurm_amd.rl.A2C for GAE '
-                                      'or normalised returns')
+                 use_gae: bool = False, normalise_returns: bool = False, gae_lambda: float = None):
+        if normalise_returns:
+            raise NotImplementedError('the fused learner does not normalise returns: use wurm_amd.rl.A2C for that')
+        if use_gae and gae_lambda is None:
+            raise NotImplementedError('use_gae=True needs gae_lambda: pass FusedA2CLearner(..., gae_lambda=0.95)')
         if value_loss not in VALUE_LOSSES:
             raise NotImplementedError(f"value_loss {value_loss!r}: the fused learner has 'smooth_l1' and 'mse'")
         flat = pack_policy_params(agent)  # raises NotImplementedError for any other architecture
@@ -53,6 +62,10 @@ class FusedA2CLearner(object):
         self.lr, self.gamma, self.entropy_coef, self.max_grad_norm = float(lr), float(gamma), float(entropy_coef), float(max_grad_norm)
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         self.value_loss = VALUE_LOSSES[value_loss]
+        self.use_gae = bool(use_gae)
+        self.gae_lambda = float(gae_lambda) if use_gae else None
+        # gamma * lambda is one Python float in the reference (a2c.py:56), rounded once: as wurm_amd.rl.a2c_returns does
+        self.gamma_lambda = float(np.float32(self.gamma * self.gae_lambda)) if use_gae else 0.0
         self.step = 0
         self.exp_avg = torch.zeros_like(flat)
         self.exp_avg_sq = torch.zeros_like(flat)
@@ -94,29 +107,38 @@ class FusedA2CLearner(object):
     def _outputs(self, N, T):
         dev = self.params.device
         return (torch.empty_like(self.params), torch.empty(3, dtype=torch.float32, device=dev),
-                torch.empty((T, N), dtype=torch.float32, device=dev))
+                torch.empty((T, N), dtype=torch.float32, device=dev),
+                torch.empty((T, N), dtype=torch.float32, device=dev) if self.use_gae else None)
 
     @staticmethod
-    def _losses(losses, values):
-        return {'value_loss': losses[0], 'policy_loss': losses[1], 'entropy': losses[2], 'values': values}
+    def _losses(losses, values, returns):
+        res = {'value_loss': losses[0], 'policy_loss': losses[1], 'entropy': losses[2], 'values': values}
+        if returns is not None:
+            res['returns'] = returns
+        return res
+
+    def _gae_args(self, returns):
+        return (ctypes.c_float(self.gamma_lambda), _lib.ptr(returns)) if self.use_gae else ()
 
     # ------------------------------------------------------------------ the two calls
 
     def grad(self, state: torch.Tensor, out: dict):
         """(flat_grad, losses): the unclipped gradient of the loss in `pack_policy_params` order and a dict of 0-dim
-        device tensors `value_loss`, `policy_loss`, `entropy` (+ `values`, (T, N): the value of every policy input).
+        device tensors `value_loss`, `policy_loss`, `entropy` (+ `values`, (T, N): the value of every policy input; with
+        GAE also `returns`, (T, N)).
         state: the observation the rollout started from; out: what `policy_rollout` returned (or any dict with
         `observations` (T,N,...), `actions`, `rewards`, `dones` (T,N))."""
         x0, obs, actions, rewards, dones, (ws, nbytes), N, T = self._inputs(state, out)
-        grad, losses, values = self._outputs(N, T)
+        grad, losses, values, returns = self._outputs(N, T)
         dev = self.params.device
-        rc = _lib.call(dev.index, _lib.lib().wurm_a2c_ff_grad, _lib.ptr(self.params), _lib.ptr(x0), _lib.ptr(obs),
+        fn = _lib.lib().wurm_a2c_ff_grad_gae if self.use_gae else _lib.lib().wurm_a2c_ff_grad
+        rc = _lib.call(dev.index, fn, _lib.ptr(self.params), _lib.ptr(x0), _lib.ptr(obs),
                        _lib.ptr(actions), _lib.ptr(rewards), _lib.ptr(dones), ctypes.c_float(self.gamma),
                        ctypes.c_float(self.entropy_coef), self.value_loss, _lib.ptr(grad), _lib.ptr(losses),
                        _lib.ptr(values), _lib.ptr(ws), _lib.i64(nbytes), _lib.i64(N), _lib.i64(T), self.num_inputs,
-                       _lib.stream_ptr(dev.index))
+                       _lib.stream_ptr(dev.index), *self._gae_args(returns))
         _lib.check(rc, 'FusedA2CLearner.grad')
-        return grad, self._losses(losses, values)
+        return grad, self._losses(losses, values, returns)
 
     def apply(self, grad: torch.Tensor) -> torch.Tensor:
         """clip_grad_norm_ + one Adam step on a flat gradient (not modified); returns its norm (0-dim device tensor)."""
@@ -140,19 +162,21 @@ class FusedA2CLearner(object):
         """One optimiser step from one rollout window: the losses of `grad` plus `grad_norm` (before clipping) and
         `grad` (unclipped), all device tensors — nothing is copied to the host."""
         x0, obs, actions, rewards, dones, (ws, nbytes), N, T = self._inputs(state, out)
-        grad, losses, values = self._outputs(N, T)
+        grad, losses, values, returns = self._outputs(N, T)
         dev = self.params.device
         norm = torch.empty(1, dtype=torch.float32, device=dev)
-        rc = _lib.call(dev.index, _lib.lib().wurm_a2c_ff_update, _lib.ptr(self.params), _lib.ptr(x0), _lib.ptr(obs),
+        fn = _lib.lib().wurm_a2c_ff_update_gae if self.use_gae else _lib.lib().wurm_a2c_ff_update
+        rc = _lib.call(dev.index, fn, _lib.ptr(self.params), _lib.ptr(x0), _lib.ptr(obs),
                        _lib.ptr(actions), _lib.ptr(rewards), _lib.ptr(dones), ctypes.c_float(self.gamma),
                        ctypes.c_float(self.entropy_coef), self.value_loss, _lib.ptr(grad), _lib.ptr(losses),
                        _lib.ptr(values), _lib.ptr(ws), _lib.i64(nbytes), _lib.i64(N), _lib.i64(T), self.num_inputs,
                        _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(norm), _lib.i64(self.step + 1),
                        ctypes.c_float(self.lr), ctypes.c_float(self.betas[0]), ctypes.c_float(self.betas[1]),
-                       ctypes.c_float(self.eps), ctypes.c_float(self.max_grad_norm), _lib.stream_ptr(dev.index))
+                       ctypes.c_float(self.eps), ctypes.c_float(self.max_grad_norm), _lib.stream_ptr(dev.index),
+                       *self._gae_args(returns))
         _lib.check(rc, 'FusedA2CLearner.update')
         self.step += 1
-        res = self._losses(losses, values)
+        res = self._losses(losses, values, returns)
         res['grad_norm'] = norm[0]
         res['grad'] = grad
         return res

@@ -240,6 +240,20 @@ def test_large_batches_default_routing(hip, N, epw):
         _compare_rollout(o, h, envs, rng.randint(0, 4, size=(T, N)).astype(np.int64), 'partial_2')
 
 
+@pytest.mark.parametrize('N', [8188, 8192])
+def test_both_sides_of_the_switch_to_four_waves_per_workgroup(hip, N):
+    """At 4 envs per wave 8 188 envs are 2 047 waves — one per workgroup — and 8 192 envs 2 048 — four per workgroup
+    (lane_launch.hpp; at the automatic envs per wave no batch below 131 072 envs gets there)."""
+    T = 3
+    rng = np.random.RandomState(N)
+    o, h = OracleBackend(seed=41), hip(seed=41)
+    envs = _fresh(o, N)
+    o.call = h.call = 1
+    with lane_path(4):
+        _compare_rollout(o, h, envs, rng.randint(0, 4, size=(T, N)).astype(np.int64), 'partial_2')
+        assert _route() == 'lane_rollout'
+
+
 def test_reference_tape_injected_through_the_lane_kernel(hip):
     """tests/golden/single_s9_partial2.npz — 48 envs x 150 steps of the REAL reference (random outcomes recorded:
     food cells, reset seed / direction / food) — replayed through lane_rollout_kernel<16, partial, INJ>."""

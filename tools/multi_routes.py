@@ -6,13 +6,19 @@
                rocprofv3 --kernel-trace --output-format csv -d DIR -o NAME -- python3 tools/multi_routes.py run [--root TREE]
            (no counters, no other tracing).  --root: the checkout whose wurm_amd / tests / oracle are imported (another
            revision, built); the cases are always this checkout's.
-  compare  two such kernel traces, row by row over the library's MultiSnake kernels (the backend's torch copies and fills
-           are dropped by name): kernel name, grid size, workgroup size, LDS size.  Exit status 1 on a difference.
-               python3 tools/multi_routes.py compare BASE_kernel_trace.csv HEAD_kernel_trace.csv > profiles/rNN_multi_routes.txt"""
+  lanes    the same for the one-env-per-lane kernels of SingleSnake / SimpleGridworld: the cases of tests/test_dispatch_table.py
+           that take a lane row (its own functions: oracle parity and the route's name are asserted), then launches on both
+           sides of every switch from one wave per workgroup to four, a per-call step and a rollout at 10 x 10, and a
+           SimpleGridworld rollout of 6 144 envs.  Compared with --pattern lane_.
+  compare  two such kernel traces, row by row over the library's kernels whose name contains --pattern (default
+           wurm::multi_; the backend's torch copies and fills are dropped by name): kernel name, grid size, workgroup size,
+           LDS size.  Exit status 1 on a difference.
+               python3 tools/multi_routes.py compare [--pattern P] BASE_kernel_trace.csv HEAD_kernel_trace.csv > profiles/rNN_multi_routes.txt"""
 import argparse
 import csv
 import importlib.util
 import os
+import re
 import sys
 
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,19 +44,78 @@ def run(root):
         print('too large: unsupported, no launch')
 
 
-def rows(path):
+def run_lanes(root):
+    sys.path.insert(0, os.path.abspath(root))
+    spec = importlib.util.spec_from_file_location('dispatch_cases', os.path.join(HERE, 'tests', 'test_dispatch_table.py'))
+    cases = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(cases)
+    import numpy as np
+    from tests.hip_backend import HipBackend
+    from wurm_amd._lib import knobs
+    for row in cases.ROLLOUT_ROWS:
+        if row[-1].startswith('lane'):
+            cases.test_rollout_rows(HipBackend, *row)
+            print('rollout row', row, cases._route(), flush=True)
+    for row in cases.STEP_ROWS:
+        if row[-1].startswith('lane'):
+            cases.test_step_rows(HipBackend, *row)
+            print('step row', row, cases._route(), flush=True)
+    cases.test_gridworld_calls_are_generic_and_large_rollouts_take_the_lane_row(HipBackend)
+    print('gridworld rows', flush=True)
+
+    h = HipBackend(seed=1)
+
+    def fresh(N, S):
+        envs = np.zeros((N, 3, S, S), np.float32)
+        h.single_reset(envs, np.ones(N, np.uint8), 'none')
+        return envs
+
+    def rollout(N, S, mode, T=3, **kn):
+        with knobs(WURM_LANE_ROLLOUT_MIN_ENVS=0, **kn):
+            h.single_rollout(fresh(N, S), np.zeros((T, N), np.int64), mode)
+        print('rollout', N, S, mode, kn, cases._route(), flush=True)
+
+    def percall(N, S, mode, **kn):  # on the mirror: its build launch, then the step with both observations
+        with knobs(**kn):
+            h.single_step_reset(fresh(N, S), np.zeros(N, np.int64), mode, call=1, want_obs_after=True, resident={'valid': 0, 'lazy': True})
+        print('per-call step', N, S, mode, kn, cases._route(), flush=True)
+
+    for N in (8188, 8192):                                  # 2 047 / 2 048 waves of a rollout
+        rollout(N, 9, 'partial_2', WURM_LANE_ROLLOUT_EPW=4)
+        rollout(N, 9, 'raw', WURM_LANE_ROLLOUT_EPW=4)       # (four waves: past 64 KB of LDS)
+    rollout(16376, 10, 'partial_2', WURM_LANE_ROLLOUT_EPW=8)
+    rollout(16384, 10, 'partial_2', WURM_LANE_ROLLOUT_EPW=8)
+    for N in (16368, 16384):                                # 1 023 / 1 024 waves of a per-call kernel
+        percall(N, 9, 'partial_2', WURM_RESIDENT_EPW=16)
+        percall(N, 9, 'raw', WURM_RESIDENT_EPW=16)
+        percall(N, 10, 'default', WURM_RESIDENT_EPW=16)
+    for N in (8192, 8196, 24576, 49152):                    # lane_step_kernel: one wave up to 8 192 envs; 4, 8, 16 envs per wave
+        with knobs(WURM_LANE_STEP_MIN_ENVS=0):
+            h.single_step(fresh(N, 9 if N != 8196 else 10), np.zeros(N, np.int64), 'partial_2')
+        print('step', N, cases._route(), flush=True)
+    g = np.zeros((6144, 2, 9, 9), np.float32)
+    h.grid_reset(g, np.ones(6144, np.uint8), (4, 4), 'default')
+    for mode in ('default', 'raw', 'positions'):
+        h.grid_rollout(g, np.zeros((3, 6144), np.int64), (4, 4), mode)
+        print('gridworld rollout', 6144, mode, cases._route(), flush=True)
+    with knobs(WURM_LANE_STEP_MIN_ENVS=0):
+        h.grid_step(g, np.zeros(6144, np.int64), 'default')
+    print('gridworld step', 6144, cases._route(), flush=True)
+
+
+def rows(path, pattern):
     out = []
     with open(path) as f:
         for r in csv.DictReader(f):
-            if 'wurm::multi_' in r['Kernel_Name']:
-                out.append((r['Kernel_Name'].replace('void ', '').replace('(wurm::MultiArgs)', '').replace('wurm::', ''),
+            if pattern in r['Kernel_Name']:
+                out.append((re.sub(r'\(wurm::\w+\)', '', r['Kernel_Name'].replace('void ', '')).replace('wurm::', ''),
                             int(r['Grid_Size_X']), int(r['Workgroup_Size_X']), int(r['LDS_Block_Size'])))
     return out
 
 
-def compare(base, head):
-    b, h = rows(base), rows(head)
-    print(f'# MultiSnake kernels of two rocprofv3 --kernel-trace runs of tools/multi_routes.py run, in order of dispatch: {len(b)} / {len(h)} rows')
+def compare(base, head, pattern):
+    b, h = rows(base, pattern), rows(head, pattern)
+    print(f'# kernels named *{pattern}* of two rocprofv3 --kernel-trace runs of tools/multi_routes.py, in order of dispatch: {len(b)} / {len(h)} rows')
     print(f'# {"#":>3s} {"same":4s} {"grid":>6s} {"wg":>4s} {"lds":>7s}  kernel (base; head beside it where it differs)')
     bad = len(b) != len(h)
     for i in range(max(len(b), len(h))):
@@ -64,8 +129,9 @@ def compare(base, head):
 
 if __name__ == '__main__':
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('what', choices=['run', 'compare'])
+    ap.add_argument('what', choices=['run', 'lanes', 'compare'])
     ap.add_argument('traces', nargs='*')
     ap.add_argument('--root', default=HERE)
-    a = ap.parse_args()
-    sys.exit(run(a.root) if a.what == 'run' else compare(*a.traces))
+    ap.add_argument('--pattern', default='wurm::multi_', help='compare: the rows whose kernel name contains this')
+    a = ap.parse_intermixed_args()
+    sys.exit(run(a.root) if a.what == 'run' else run_lanes(a.root) if a.what == 'lanes' else compare(*a.traces, a.pattern))

@@ -20,6 +20,7 @@
 // done[0][env] = GRID_SKIPPED; the one-env-per-wave code rolls it out in a second launch (flagged_kernel), exactly as
 // behind the clock-grid kernels (grid_rollout.hip).  RNG mode only (recorded outcomes take the generic kernel).
 // Integer / index work: no MFMA.
+#include "lane_launch.hpp"
 #include "options.hpp"
 #include "step_args.hpp"
 
@@ -515,25 +516,17 @@ constexpr int GWL_SLAB_MAX = 16384; // bytes per wave of the image modes' bit st
 static long long gwl_slab_bytes(long long floats) { return (((floats + 31) / 32) * 4 + 15) & ~15ll; }
 
 // The slabs of a workgroup's four waves can reach 64 KB of DYNAMIC LDS, and the kernels keep 5 KB of static scan state beside
-// them: past the 64 KB a launch gets by default the kernel is opted into the larger budget, as lane_rollout's launcher does
+// them: lane_launch is told so, and past the 64 KB a launch gets by default it opts the kernel into the larger budget
 // (it only worked because the runtime does not enforce the opt-in on a 160 KB part).
-static void gwl_allow_lds(const void *kernel, size_t dynamic_bytes)
-{
-    if (dynamic_bytes + sizeof(GridLaneScan) * 4 > 65536)
-        (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dynamic_bytes);
-}
+constexpr size_t GWL_STATIC_LDS = sizeof(GridLaneScan) * 4;
 
 template <int OBS, int EPW>
 static void launch_epw(const StepArgs &p0, hipStream_t stream)
 {
     StepArgs p = p0;
-    const long long waves = (p.N + EPW - 1) / EPW;
-    const int wpb = 4;
-    const dim3 block(64 * wpb), grid((unsigned)((waves + wpb - 1) / wpb));
     const long long slab = (OBS == WURM_OBS_DEFAULT || OBS == WURM_OBS_RAW) ? gwl_slab_bytes(EPW * p.obs_elems) : 0;
     p.lds_per_wave = slab <= GWL_SLAB_MAX ? (int)slab : 0;
-    gwl_allow_lds((const void *)gridworld_lane_rollout_kernel<OBS, EPW>, (size_t)p.lds_per_wave * wpb);
-    WURM_LAUNCH((gridworld_lane_rollout_kernel<OBS, EPW>), grid, block, (size_t)p.lds_per_wave * wpb, stream, p);
+    lane_launch(gridworld_lane_rollout_kernel<OBS, EPW>, p, p.N, EPW, 0, 0, p.lds_per_wave, stream, GWL_STATIC_LDS); // (always four waves)
 }
 
 template <int OBS>
@@ -606,12 +599,8 @@ template <int OBS, int EPW>
 static void launch_step_epw(const StepArgs &p0, hipStream_t stream)
 {
     StepArgs p = p0;
-    const long long waves = (p.N + EPW - 1) / EPW;
-    const int wpb = 4;
-    const dim3 block(64 * wpb), grid((unsigned)((waves + wpb - 1) / wpb));
     p.lds_per_wave = (OBS == WURM_OBS_DEFAULT || OBS == WURM_OBS_RAW) ? (int)gwl_slab_bytes(EPW * p.obs_elems) : 0;
-    gwl_allow_lds((const void *)gridworld_lane_step_kernel<OBS, EPW>, (size_t)p.lds_per_wave * wpb);
-    WURM_LAUNCH((gridworld_lane_step_kernel<OBS, EPW>), grid, block, (size_t)p.lds_per_wave * wpb, stream, p);
+    lane_launch(gridworld_lane_step_kernel<OBS, EPW>, p, p.N, EPW, 0, 0, p.lds_per_wave, stream, GWL_STATIC_LDS);
 }
 
 template <int OBS>
@@ -639,9 +628,7 @@ long long gridworld_resident_bytes(long long N, int S, int obs_mode, long long o
 hipError_t launch_gridworld_lane_flush(const StepArgs &p, hipStream_t stream)
 {
     (void)hipGetLastError();
-    constexpr int EPW = 16, wpb = 4;
-    const long long waves = (p.N + EPW - 1) / EPW;
-    WURM_LAUNCH((gridworld_lane_flush_kernel<EPW>), dim3((unsigned)((waves + wpb - 1) / wpb)), dim3(64 * wpb), 0, stream, p);
+    lane_launch(gridworld_lane_flush_kernel<16>, p, p.N, 16, 0, 0, 0, stream);
     return hipGetLastError();
 }
 

@@ -17,7 +17,8 @@
 //
 // One env per lane for the transition; crops of the post-step state (`obs`) and, when asked for, of the state after the
 // finished envs are rebuilt (`obs_after`, what reset(done) returns) as (which, env) pair lanes -> bit planes -> flat bit
-// strings -> 256-entry float4 table -> aligned 16-byte stores, exactly as phases 3 and 4 of lane_rollout_kernel.
+// strings -> 256-entry float4 table -> aligned 16-byte stores, exactly as phases 3 and 4 of lane_rollout_kernel (the shared
+// pieces: lane_planes.hpp; the launch: lane_launch.hpp).
 // Contract: fused_step_kernel's without post_reset (deferred reset: envs flagged in p.done_in are rebuilt in front of the
 // step with call = p.pre_call).  Domain: S = 9, observation 'partial_2' or none, RNG mode; per env the domain of
 // lane_rollout.hpp.  An env outside it — or one that finished and is stepped again without the reset — is stepped by
@@ -160,7 +161,7 @@ struct ResLds {
 // behind ResLds::BYTES
 constexpr int res_wave_bytes(int OBSK)
 {
-    return ResLds::BYTES + (OBSK == LR_OBS_RAW ? LR_RAW_SLAB : (OBSK == LR_OBS_GRID1 || OBSK == LR_OBS_GRID3 || OBSK == LR_OBS_CROP3) ? LR_GRID_BITS : 0);
+    return ResLds::BYTES + (OBSK == LR_OBS_RAW ? LR_RAW_SLAB : (OBSK == LANE_OBS_GRID1 || OBSK == LANE_OBS_GRID3 || OBSK == LR_OBS_CROP3) ? LR_GRID_BITS : 0);
 }
 
 // EPW envs per wave; NW = 2: crops of `obs` and of `obs_after` (EPW * 2 <= 64 pair lanes), NW = 1: `obs` only; LAZY: `envs`
@@ -170,13 +171,13 @@ __global__ __launch_bounds__(256) void lane_resident_step_kernel(ResidentArgs a)
 {
     static_assert(EPW == 16 || EPW == 32 || EPW == 64, "envs per wave");
     static_assert(EPW * NW <= 64 && (NW == 1 || NW == 2), "pair lanes");
-    static_assert(OBSK == WURM_OBS_PARTIAL || OBSK == LR_OBS_GENERIC || OBSK == LR_OBS_GRID1 || OBSK == LR_OBS_GRID3 ||
+    static_assert(OBSK == WURM_OBS_PARTIAL || OBSK == LR_OBS_GENERIC || OBSK == LANE_OBS_GRID1 || OBSK == LANE_OBS_GRID3 ||
                   OBSK == LR_OBS_CROP3 || OBSK == LR_OBS_RAW || (OBSK == WURM_OBS_NONE && NW == 1),
                   "partial_2, one_channel / default / partial_3 through bit planes, raw through bytes, any other mode at run time (lr_obs_value), or none");
-    constexpr bool GRID = OBSK == LR_OBS_GRID1 || OBSK == LR_OBS_GRID3 || OBSK == LR_OBS_CROP3;
+    constexpr bool GRID = OBSK == LANE_OBS_GRID1 || OBSK == LANE_OBS_GRID3 || OBSK == LR_OBS_CROP3;
     constexpr bool RAW = OBSK == LR_OBS_RAW;
     constexpr bool GTAB = lr_grid_tables(OBSK);
-    constexpr int GE = OBSK == LR_OBS_GRID1 ? LR_C : OBSK == LR_OBS_CROP3 ? LR_E3 : LR_C3; // floats per env of such a mode
+    constexpr int GE = OBSK == LANE_OBS_GRID1 ? LR_C : OBSK == LR_OBS_CROP3 ? LR_E3 : LR_C3; // floats per env of such a mode
     constexpr int S = 9, C = LR_C, C3 = LR_C3;
     constexpr int LOG_EPW = EPW == 16 ? 4 : EPW == 32 ? 5 : 6;
     constexpr int NP = EPW * NW;                 // pair lanes
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(256) void lane_resident_step_kernel(ResidentArgs a)
         __syncthreads();
     } else if (OBSK == LR_OBS_GENERIC || GRID) {
         lr_build_lut(lut, p.obs_mode, p.obs_n, (int)p.obs_elems);
-        if (GRID) lr_build_grid_tables<OBSK>(tab, tabB);
+        if (GRID) lane_build_tables<OBSK>(tab, tabB);
         if (OBSK == LR_OBS_CROP3) lr_build_wint7(wint); // (in the place of 'one_channel's second table)
         __syncthreads();
     }
@@ -438,7 +439,7 @@ __global__ __launch_bounds__(256) void lane_resident_step_kernel(ResidentArgs a)
         }
         if (lane < EPW) { io[lane] = cr; if (NW == 2) io[EPW + lane] = cr2; }
         if (GRID && nenv == EPW) {
-            constexpr int GPL = OBSK == LR_OBS_GRID1 ? 4 : 2;
+            constexpr int GPL = lane_plane_count<OBSK>();
             constexpr int NWORDS = GPL * ((NP * GE + 31) / 32 + 4);
             static_assert(NWORDS * 4 + 16 <= LR_GRID_BITS, "flat bit strings of a grid mode");
             for (int i = lane; i < (NWORDS + 3) / 4; i += 64) ((uint4 *)gbits)[i] = make_uint4(0, 0, 0, 0);
@@ -460,7 +461,7 @@ __global__ __launch_bounds__(256) void lane_resident_step_kernel(ResidentArgs a)
             float4 *ob0 = (float4 *)(p.obs + env0 * GE), *ob1 = NW == 2 ? (float4 *)(p.obs_after + env0 * GE) : nullptr;
 #pragma unroll 4
             for (int j = lane; j < NW * GSG; j += 64) {
-                const float4 v = lr_grid_group<OBSK>(gbits, tab, tabB, j);
+                const float4 v = lane_group<OBSK>(gbits, tab, tabB, j);
                 const bool second = NW == 2 && j >= GSG;
                 (second ? ob1 : ob0)[second ? j - GSG : j] = v;
             }
@@ -571,11 +572,8 @@ hipError_t launch_lane_resident_flush(const StepArgs &p, void *resident, hipStre
     a.res = (uint4 *)resident;
     a.check_mask = nullptr;
     constexpr int EPW = 16;
-    const long long waves = (p.N + EPW - 1) / EPW;
-    const int wpb = waves >= 1024 ? 4 : 1;
-    dim3 block(64 * wpb), grid((unsigned)((waves + wpb - 1) / wpb));
     (void)hipGetLastError();
-    WURM_LAUNCH(lane_resident_flush_kernel<EPW>, grid, block, (size_t)((EPW * LR_C3 + 16) * wpb), stream, a);
+    lane_launch(lane_resident_flush_kernel<EPW>, a, p.N, EPW, 1024, 0, EPW * LR_C3 + 16, stream);
     return hipGetLastError();
 }
 
@@ -589,10 +587,7 @@ static hipError_t launch_lane_resident_form(const StepArgs &p, void *resident, b
     (void)hipGetLastError();
     if (!valid) {
         constexpr int EPW = 16;
-        const long long waves = (p.N + EPW - 1) / EPW;
-        const int wpb = waves >= 1024 ? 4 : 1;
-        dim3 block(64 * wpb), grid((unsigned)((waves + wpb - 1) / wpb));
-        WURM_LAUNCH(lane_resident_build_kernel<EPW>, grid, block, (size_t)(LaneRollLds<EPW>::BYTES * wpb), stream, a);
+        lane_launch(lane_resident_build_kernel<EPW>, a, p.N, EPW, 1024, 0, LaneRollLds<EPW>::BYTES, stream);
         hipError_t err = hipGetLastError();
         if (err != hipSuccess) return err;
     }
@@ -607,14 +602,9 @@ static hipError_t launch_lane_resident_form(const StepArgs &p, void *resident, b
     // with the reset observation; 32 768 envs 6.3 / 5.9 / 6.3 and 7.6 / 8.4 / -
     if (epw != 16 && epw != 32 && epw != 64) epw = nw == 1 ? (p.N >= 16384 ? 32 : 16) : (p.N >= 49152 ? 32 : 16);
     if (epw * nw > 64) epw = 32;
-    const int obsk = grid1 ? LR_OBS_GRID1 : grid3 ? LR_OBS_GRID3 : crop3 ? LR_OBS_CROP3 : raw ? LR_OBS_RAW : 0;
+    const int obsk = grid1 ? LANE_OBS_GRID1 : grid3 ? LANE_OBS_GRID3 : crop3 ? LR_OBS_CROP3 : raw ? LR_OBS_RAW : 0;
     auto go = [&](auto kernel, int e) {
-        const long long waves = (p.N + e - 1) / e;
-        const int wpb = waves >= 1024 ? 4 : 1;
-        dim3 block(64 * wpb), grid((unsigned)((waves + wpb - 1) / wpb));
-        const size_t lds_bytes = (size_t)((lr_grid_tables(obsk) ? LR_TAB_GRID : LR_TAB) + res_wave_bytes(obsk) * wpb);
-        if (lds_bytes > 65536) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        WURM_LAUNCH(kernel, grid, block, lds_bytes, stream, a);
+        lane_launch(kernel, a, p.N, e, 1024, lr_grid_tables(obsk) ? LR_TAB_GRID : LR_TAB, res_wave_bytes(obsk), stream);
     };
     if (crop3) {
         if (nw == 2) {
@@ -632,18 +622,18 @@ static hipError_t launch_lane_resident_form(const StepArgs &p, void *resident, b
         else go(lane_resident_step_kernel<64, 1, LR_OBS_RAW, LAZY>, 64);
     } else if (grid1) {
         if (nw == 2) {
-            if (epw == 16) go(lane_resident_step_kernel<16, 2, LR_OBS_GRID1, LAZY>, 16);
-            else go(lane_resident_step_kernel<32, 2, LR_OBS_GRID1, LAZY>, 32);
-        } else if (epw == 16) go(lane_resident_step_kernel<16, 1, LR_OBS_GRID1, LAZY>, 16);
-        else if (epw == 32) go(lane_resident_step_kernel<32, 1, LR_OBS_GRID1, LAZY>, 32);
-        else go(lane_resident_step_kernel<64, 1, LR_OBS_GRID1, LAZY>, 64);
+            if (epw == 16) go(lane_resident_step_kernel<16, 2, LANE_OBS_GRID1, LAZY>, 16);
+            else go(lane_resident_step_kernel<32, 2, LANE_OBS_GRID1, LAZY>, 32);
+        } else if (epw == 16) go(lane_resident_step_kernel<16, 1, LANE_OBS_GRID1, LAZY>, 16);
+        else if (epw == 32) go(lane_resident_step_kernel<32, 1, LANE_OBS_GRID1, LAZY>, 32);
+        else go(lane_resident_step_kernel<64, 1, LANE_OBS_GRID1, LAZY>, 64);
     } else if (grid3) {
         if (nw == 2) {
-            if (epw == 16) go(lane_resident_step_kernel<16, 2, LR_OBS_GRID3, LAZY>, 16);
-            else go(lane_resident_step_kernel<32, 2, LR_OBS_GRID3, LAZY>, 32);
-        } else if (epw == 16) go(lane_resident_step_kernel<16, 1, LR_OBS_GRID3, LAZY>, 16);
-        else if (epw == 32) go(lane_resident_step_kernel<32, 1, LR_OBS_GRID3, LAZY>, 32);
-        else go(lane_resident_step_kernel<64, 1, LR_OBS_GRID3, LAZY>, 64);
+            if (epw == 16) go(lane_resident_step_kernel<16, 2, LANE_OBS_GRID3, LAZY>, 16);
+            else go(lane_resident_step_kernel<32, 2, LANE_OBS_GRID3, LAZY>, 32);
+        } else if (epw == 16) go(lane_resident_step_kernel<16, 1, LANE_OBS_GRID3, LAZY>, 16);
+        else if (epw == 32) go(lane_resident_step_kernel<32, 1, LANE_OBS_GRID3, LAZY>, 32);
+        else go(lane_resident_step_kernel<64, 1, LANE_OBS_GRID3, LAZY>, 64);
     } else if (generic) {
         if (nw == 2) {
             if (epw == 16) go(lane_resident_step_kernel<16, 2, LR_OBS_GENERIC, LAZY>, 16);

@@ -26,11 +26,15 @@
 // interior cells with the head on L and at most one food on a free interior cell (closed under step + reset).  Any other
 // env is left alone and rolled out by rollout_generic — the one-env-per-wave code — at the end of the same launch.
 // INJ: recorded random outcomes instead of Philox (tests/golden tapes through this kernel).
+// Shared with lane_wide.hpp: the whole-block state read (lane_load.hpp), bit planes -> floats for every mode but 'partial_2'
+// (lane_planes.hpp), the per-step output stores (store_pair_outputs, step_args.hpp), the launch (lane_launch.hpp).
 #pragma once
 
 #include <type_traits>
 
+#include "lane_launch.hpp"
 #include "lane_load.hpp"
+#include "lane_planes.hpp"
 
 namespace wurm {
 
@@ -271,7 +275,6 @@ __device__ __forceinline__ void lr_write_generic(const StepArgs &p, const uint4 
 //   'one_channel' (:142-151: 0.5 body + 0.5 head + 1.5 food, ring -1): four planes of 81 bits — body without the head
 //       (0.5), head (1.0 = 0.5 + 0.5), food (1.5), ring (-1) — and two tables whose results are ADDED: the planes exclude each
 //       other, so one of the two addends is always +0 and the sum is exact.
-constexpr int LR_OBS_GRID1 = -2, LR_OBS_GRID3 = -3;   // OBSK of the kernels: one_channel / default through bit planes
 constexpr int LR_OBS_CROP3 = -4;                      // 'partial_3' (round 5): 7 x 7 crops through the same bit planes, 147 floats per env
 constexpr int LR_OBS_RAW = -5;                        // 'raw' (round 5): the state itself, through one byte per float
 constexpr int LR_E3 = 147;                            // floats of a 7 x 7 crop
@@ -314,7 +317,7 @@ __device__ __forceinline__ void lr_grid_planes(u32 *bits, int p, u64 oc, int hy,
     const int hp = 9 * hy + hx, fp = fc >= 0 ? 9 * (fc >> 3) + (fc & 7) : -1;
     const u64 hlo = hin && hp < 64 ? 1ull << hp : 0ull, flo = fp >= 0 && fp < 64 ? 1ull << fp : 0ull;
     const u32 hhi = hin && hp >= 64 ? 1u << (hp - 64) : 0u, fhi = fp >= 64 ? 1u << (fp - 64) : 0u;
-    if (OBSK == LR_OBS_GRID1) {
+    if (OBSK == LANE_OBS_GRID1) {
         const int off = LR_C * p;
         lr_or81<4>(bits, 0, off, olo & ~hlo, ohi & ~hhi);           // body without the head: 0.5
         lr_or81<4>(bits, 1, off, hlo, hhi);                         // head: 1.0
@@ -329,39 +332,6 @@ __device__ __forceinline__ void lr_grid_planes(u32 *bits, int p, u64 oc, int hy,
         lr_or81<2>(bits, 0, off + 2 * LR_C, free_lo, free_hi);                // B: free
         lr_or81<2>(bits, 1, off + LR_C, olo & ~hlo, ohi & ~hhi);              // G = 127/255: body
     }
-}
-
-// tables of the grid modes: tabA as lr_build_tables's for 'default'; for 'one_channel' tabA[low nibble: 0.5, high: 1.0],
-// tabB[low nibble: 1.5, high: -1.0]
-template <int OBSK>
-__device__ __forceinline__ void lr_build_grid_tables(float4 *tabA, float4 *tabB)
-{
-    for (int i = (int)threadIdx.x; i < 256; i += (int)blockDim.x) {
-        float a[4], b[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bool lo = ((i >> j) & 1) != 0, hi = ((i >> (4 + j)) & 1) != 0;
-            if (OBSK == LR_OBS_GRID1) { a[j] = lo ? 0.5f : hi ? 1.0f : 0.0f; b[j] = lo ? 1.5f : hi ? -1.0f : 0.0f; }
-            else { a[j] = lo ? 1.0f : hi ? 127.0f / 255.0f : 0.0f; b[j] = 0.0f; }
-        }
-        tabA[i] = make_float4(a[0], a[1], a[2], a[3]);
-        if (OBSK == LR_OBS_GRID1) tabB[i] = make_float4(b[0], b[1], b[2], b[3]);
-    }
-}
-
-// 16-byte group j of a flat run of floats whose bits start at bit 0 of the strings -> four floats
-template <int OBSK>
-__device__ __forceinline__ float4 lr_grid_group(const u32 *bits, const float4 *tabA, const float4 *tabB, int j)
-{
-    const int w = j >> 3, sh = (j & 7) * 4;
-    if (OBSK == LR_OBS_GRID1) {
-        const uint4 q = ((const uint4 *)bits)[w];
-        const float4 a = tabA[((q.x >> sh) & 15u) | (((q.y >> sh) & 15u) << 4)];
-        const float4 b = tabB[((q.z >> sh) & 15u) | (((q.w >> sh) & 15u) << 4)];
-        return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-    }
-    const uint2 q = ((const uint2 *)bits)[w];
-    return tabA[((q.x >> sh) & 15u) | (((q.y >> sh) & 15u) << 4)];
 }
 
 // ---- 'partial_3' (round 5): the 7 x 7 window of the occupancy mask around the head is still ONE 64-bit shift (window bit
@@ -387,18 +357,6 @@ __device__ __forceinline__ u64 lr_compact7(u64 x)
            ((x >> 4) & (0x7Full << 28)) | ((x >> 5) & (0x7Full << 35)) | ((x >> 6) & (0x7Full << 42));
 }
 
-// ORs 49 bits into plane k of NPL interleaved flat bit strings at bit offset off
-template <int NPL>
-__device__ __forceinline__ void lr_or49(u32 *bits, int k, int off, u64 v)
-{
-    const int w = off >> 5, sb = off & 31;
-    const u64 a = (u64)(u32)v << sb, b = (u64)(u32)(v >> 32) << sb;
-    u32 *P = bits + NPL * w + k;
-    atomicOr(&P[0], (u32)a);
-    atomicOr(&P[NPL], (u32)(a >> 32) | (u32)b);
-    if ((u32)(b >> 32)) atomicOr(&P[2 * NPL], (u32)(b >> 32));
-}
-
 // planes of pair p: occupancy oc of the stepped state, head (hy, hx) — also on the ring —, food code fc (-1: none)
 __device__ __forceinline__ void lr_crop3_planes(u32 *bits, const u64 *wint7, int p, u64 oc, int hy, int hx, int fc)
 {
@@ -407,16 +365,12 @@ __device__ __forceinline__ void lr_crop3_planes(u32 *bits, const u64 *wint7, int
     const u64 W = wint7[hy * 9 + hx];
     const int fpos_w = fc - sh;
     const u64 F = fc >= 0 && (unsigned)fpos_w < 56u ? (1ull << fpos_w) & W : 0ull;
-    const u64 R = W & ~V;                         // free or food: red
-    const u64 B = R & ~F;                         // free: blue (and green)
-    const u64 CENTRE = 1ull << 27;
-    const u64 G1 = B | (W & CENTRE);              // green 1: free, or the head inside the ring
-    const u64 GH = V & W & ~CENTRE;               // green 127/255: body
+    const LaneCrop k = lane_crop_colours(V, W, F, 1ull << 27);
     const int off = LR_E3 * p;
-    lr_or49<2>(bits, 0, off, lr_compact7(R));
-    lr_or49<2>(bits, 0, off + 49, lr_compact7(G1));
-    lr_or49<2>(bits, 0, off + 98, lr_compact7(B));
-    lr_or49<2>(bits, 1, off + 49, lr_compact7(GH));
+    lane_or64<2>(bits, 0, off, lr_compact7(k.R));
+    lane_or64<2>(bits, 0, off + 49, lr_compact7(k.G1));
+    lane_or64<2>(bits, 0, off + 98, lr_compact7(k.B));
+    lane_or64<2>(bits, 1, off + 49, lr_compact7(k.GH));
 }
 
 // per-wave LDS of lane_rollout_kernel<EPW, OBSK, ·>: the grid / crop modes keep their flat bit strings behind
@@ -427,10 +381,10 @@ constexpr int lr_wave_bytes()
 {
     typedef LaneRollLds<EPW> Lds;
     if (OBSK == LR_OBS_RAW) return Lds::BYTES > Lds::SCR + LR_RAW_SLAB ? Lds::BYTES : ((Lds::SCR + LR_RAW_SLAB + 15) & ~15);
-    if (OBSK == LR_OBS_GRID1 || OBSK == LR_OBS_GRID3 || OBSK == LR_OBS_CROP3) return Lds::BYTES + LR_GRID_BITS;
+    if (OBSK == LANE_OBS_GRID1 || OBSK == LANE_OBS_GRID3 || OBSK == LR_OBS_CROP3) return Lds::BYTES + LR_GRID_BITS;
     return Lds::BYTES;
 }
-constexpr bool lr_grid_tables(int OBSK) { return OBSK == LR_OBS_GRID1 || OBSK == LR_OBS_GRID3 || OBSK == LR_OBS_CROP3 || OBSK == LR_OBS_RAW; }
+constexpr bool lr_grid_tables(int OBSK) { return OBSK == LANE_OBS_GRID1 || OBSK == LANE_OBS_GRID3 || OBSK == LR_OBS_CROP3 || OBSK == LR_OBS_RAW; }
 
 // The state of a block of EPW consecutive envs (`block` = its first float), read cooperatively — lanes = (env, cell) pairs,
 // the few non-zero elements scattered into a per-env value -> cell table in LDS — then, per env lane: validation and the
@@ -546,14 +500,14 @@ __global__ __launch_bounds__(256) void lane_rollout_kernel(StepArgs p)
 {
     typedef LaneRollLds<EPW> Lds;
     static_assert(EPW == 4 || EPW == 8 || EPW == 16 || EPW == 32 || EPW == 64, "envs per wave");
-    static_assert(OBSK == WURM_OBS_PARTIAL || OBSK == WURM_OBS_NONE || OBSK == LR_OBS_GENERIC || OBSK == LR_OBS_GRID1 ||
-                  OBSK == LR_OBS_GRID3 || OBSK == LR_OBS_CROP3 || OBSK == LR_OBS_RAW,
+    static_assert(OBSK == WURM_OBS_PARTIAL || OBSK == WURM_OBS_NONE || OBSK == LR_OBS_GENERIC || OBSK == LANE_OBS_GRID1 ||
+                  OBSK == LANE_OBS_GRID3 || OBSK == LR_OBS_CROP3 || OBSK == LR_OBS_RAW,
                   "lane rollout: partial_2, partial_3, one_channel, default, raw, no observation, or any other mode at run time");
-    constexpr bool GRID = OBSK == LR_OBS_GRID1 || OBSK == LR_OBS_GRID3 || OBSK == LR_OBS_CROP3; // flat bit strings -> table
+    constexpr bool GRID = OBSK == LANE_OBS_GRID1 || OBSK == LANE_OBS_GRID3 || OBSK == LR_OBS_CROP3; // flat bit strings -> table
     constexpr bool RAW = OBSK == LR_OBS_RAW;                                                    // byte slab -> floats
     constexpr bool GTAB = lr_grid_tables(OBSK);                 // LDS layout of the grid modes
-    constexpr int GE = OBSK == LR_OBS_GRID1 ? LR_C : OBSK == LR_OBS_CROP3 ? LR_E3 : LR_C3; // floats per env of such a mode
-    constexpr int GPL = OBSK == LR_OBS_GRID1 ? 4 : 2;           // its interleaved bit planes
+    constexpr int GE = OBSK == LANE_OBS_GRID1 ? LR_C : OBSK == LR_OBS_CROP3 ? LR_E3 : LR_C3; // floats per env of such a mode
+    constexpr int GPL = lane_plane_count<OBSK>();               // its interleaved bit planes
     constexpr int TC = 64 / EPW;                  // steps per chunk
     constexpr int LOG_EPW = EPW == 4 ? 2 : EPW == 8 ? 3 : EPW == 16 ? 4 : EPW == 32 ? 5 : 6;
     constexpr int GS = EPW * LR_E / 4;            // 16-byte groups per step of the wave's crops
@@ -569,7 +523,7 @@ __global__ __launch_bounds__(256) void lane_rollout_kernel(StepArgs p)
     unsigned short *lut = (unsigned short *)(lr_lds + (GTAB ? 8192 : 0));
     float4 *tabB = (float4 *)(lr_lds + 4096);
     if (OBSK == LR_OBS_GENERIC || GRID) lr_build_lut(lut, p.obs_mode, p.obs_n, (int)p.obs_elems);
-    if (GRID) lr_build_grid_tables<OBSK>(tab, tabB);
+    if (GRID) lane_build_tables<OBSK>(tab, tabB);
     else if (OBSK != LR_OBS_GENERIC && !RAW) lr_build_tables(tab, wint);
     if (OBSK == LR_OBS_CROP3) lr_build_wint7(wint); // (in the place of 'one_channel's second table)
     __syncthreads();
@@ -712,13 +666,7 @@ __global__ __launch_bounds__(256) void lane_rollout_kernel(StepArgs p)
             {
                 const u32 rz = rec.z, rw = rec.w;
                 const bool valid = pv && (rw & 0x8000u) != 0;
-                if (valid) {
-                    store_action(p.actions, p.act_dtype, oi, (long long)(int)(signed char)(rz >> 8));
-                    p.reward[oi] = (rw & 0x100u) ? 1.0f : 0.0f;
-                    p.done[oi] = (uint8_t)((rw & 0x600u) != 0);
-                    p.selfc[oi] = (uint8_t)((rw >> 9) & 1u);
-                    p.edgec[oi] = (uint8_t)((rw >> 10) & 1u);
-                }
+                if (valid) store_pair_outputs(p, oi, rz, rw);
                 if (GRID && valid) { // planes of the stepped state (the head also when it is on the ring)
                     const int cp = (int)(rz & 63u), ai = (int)((rz >> 8) & 3u);
                     if constexpr (OBSK == LR_OBS_CROP3)
@@ -808,7 +756,7 @@ __global__ __launch_bounds__(256) void lane_rollout_kernel(StepArgs p)
                     const size_t step_bytes = (size_t)p.N * (GE * 4);
 #pragma unroll 4
                     for (int j = lane; j < NGRP; j += 64) {
-                        const float4 v = lr_grid_group<OBSK>(gbits, tab, tabB, j);
+                        const float4 v = lane_group<OBSK>(gbits, tab, tabB, j);
                         const int s = EPW == 64 ? 0 : j / GSG;
                         // (a float4 pointer indexed by group: through `char * + 16 j` the EPW = 64 instantiations came out with
                         // every 16-byte store split into four dword stores — see lane_resident.hpp)
@@ -959,15 +907,9 @@ static hipError_t launch_lane_rollout_obs(const StepArgs &p, hipStream_t stream)
 {
     const bool inj = p.inject_food != nullptr;
     const int epw = inj ? 16 : lane_rollout_epw_checked(p.N, p.obs_mode);
-    const long long waves = (p.N + epw - 1) / epw;
-    const int wpb = waves >= 2048 ? 4 : 1;
-    dim3 block(64 * wpb), grid((unsigned)((waves + wpb - 1) / wpb));
     (void)hipGetLastError();
     auto go = [&](auto kernel, int lds_per_wave) {
-        const size_t lds_bytes = (size_t)((lr_grid_tables(OBSK) ? LR_TAB_GRID : LR_TAB) + lds_per_wave * wpb);
-        // ('raw' with four waves per workgroup: 80 KB — beyond the 64 KB a launch gets without the kernel's opt-in)
-        if (lds_bytes > 65536) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        WURM_LAUNCH(kernel, grid, block, lds_bytes, stream, p);
+        lane_launch(kernel, p, p.N, epw, 2048, lr_grid_tables(OBSK) ? LR_TAB_GRID : LR_TAB, lds_per_wave, stream);
     };
     if (inj) go(lane_rollout_kernel<16, OBSK, true>, lr_wave_bytes<16, OBSK>());
     else if (epw == 4) go(lane_rollout_kernel<4, OBSK, false>, lr_wave_bytes<4, OBSK>());
@@ -982,8 +924,8 @@ hipError_t launch_lane_rollout(const StepArgs &p, hipStream_t stream)
 {
     if (p.obs_mode == WURM_OBS_NONE) return launch_lane_rollout_obs<WURM_OBS_NONE>(p, stream);
     if (p.obs_mode == WURM_OBS_PARTIAL && p.obs_n == 2) return launch_lane_rollout_obs<WURM_OBS_PARTIAL>(p, stream);
-    if (p.obs_mode == WURM_OBS_ONE_CHANNEL) return launch_lane_rollout_obs<LR_OBS_GRID1>(p, stream);
-    if (p.obs_mode == WURM_OBS_DEFAULT) return launch_lane_rollout_obs<LR_OBS_GRID3>(p, stream);
+    if (p.obs_mode == WURM_OBS_ONE_CHANNEL) return launch_lane_rollout_obs<LANE_OBS_GRID1>(p, stream);
+    if (p.obs_mode == WURM_OBS_DEFAULT) return launch_lane_rollout_obs<LANE_OBS_GRID3>(p, stream);
     if (p.obs_mode == WURM_OBS_PARTIAL && p.obs_n == 3) return launch_lane_rollout_obs<LR_OBS_CROP3>(p, stream);
     if (p.obs_mode == WURM_OBS_RAW) return launch_lane_rollout_obs<LR_OBS_RAW>(p, stream);
     return launch_lane_rollout_obs<LR_OBS_GENERIC>(p, stream);

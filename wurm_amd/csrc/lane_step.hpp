@@ -22,6 +22,7 @@
 // Follows single_snake.py:197-304 (step), :322-387 (reset), :130-195 (_observe) like the kernels it stands in for.
 #pragma once
 
+#include "lane_launch.hpp"
 #include "lane_load.hpp"
 #include "single_device.hpp"
 
@@ -396,14 +397,11 @@ static hipError_t launch_lane_step(const StepArgs &p, hipStream_t stream)
     // 16 384: 11.2 / 12.0 / 14.9 [15.1], 32 768: 17.4 / 15.6 / 17.6 [26.6], 65 536: 28.7 / 27.3 / 26.0 [48.3].
     const int epw = p.N >= 49152 ? 16 : (p.N >= 24576 ? 8 : 4);
     (void)hipGetLastError();
+    // one wave per workgroup up to 8 192 envs — 2 048 waves at the 4 envs per wave such a batch gets —, four beyond
     auto go = [&](auto k9, auto k10, auto k11, int epw, int lds_per_wave) {
-        const int wpb = p.N <= 8192 ? 1 : 4;
-        const long long waves = (p.N + epw - 1) / epw;
-        dim3 block(64 * wpb), grid((unsigned)((waves + wpb - 1) / wpb));
-        const size_t lds = (size_t)lds_per_wave * wpb;
-        if (p.S == 9) WURM_LAUNCH(k9, grid, block, lds, stream, a);
-        else if (p.S == 10) WURM_LAUNCH(k10, grid, block, lds, stream, a);
-        else WURM_LAUNCH(k11, grid, block, lds, stream, a);
+        if (p.S == 9) lane_launch(k9, a, p.N, epw, 2049, 0, lds_per_wave, stream);
+        else if (p.S == 10) lane_launch(k10, a, p.N, epw, 2049, 0, lds_per_wave, stream);
+        else lane_launch(k11, a, p.N, epw, 2049, 0, lds_per_wave, stream);
     };
     if (epw == 4) go(lane_step_kernel<4, 9>, lane_step_kernel<4, 10>, lane_step_kernel<4, 11>, 4, LaneLds<4>::BYTES);
     else if (epw == 8) go(lane_step_kernel<8, 9>, lane_step_kernel<8, 10>, lane_step_kernel<8, 11>, 8, LaneLds<8>::BYTES);

@@ -4,7 +4,8 @@
 // (rollout_lean_kernel / rollout_kernel) at about half of what 9 x 9 gets: 65 536 envs of 10 x 10 'partial_2' 6.4e9
 // env-steps/s against 1.15e10, 11 x 11 'default' 2.3e9 against 5.1e9 (tools/s10_s11_probe.py).
 //
-// Same four phases per chunk of TC = 64 / EPW steps as lane_rollout.hpp:
+// Same four phases per chunk of TC = 64 / EPW steps as lane_rollout.hpp (shared with it: the whole-block state read of
+// lane_load.hpp, bit planes -> floats in lane_planes.hpp, store_pair_outputs of step_args.hpp, the launch in lane_launch.hpp):
 //   (1) pair lanes ((step, env) pairs): the action -> sanitise inputs; both Philox blocks of (t, env) — the food draw and
 //       the complete would-be reset (lean_reset_draw) — or the recorded outcomes (INJ);
 //   (2) env lanes, TC steps one after another: the transition of single_snake.py:197-304 on per-lane state — a 128-bit
@@ -24,11 +25,13 @@
 // at the end of the same launch.  Every other observation mode stays with the one-env-per-wave kernels.
 #pragma once
 
+#include "lane_launch.hpp"
 #include "lane_load.hpp"
+#include "lane_planes.hpp"
 
 namespace wurm {
 
-constexpr int LW_OBS_GRID1 = -2, LW_OBS_GRID3 = -3; // OBSK: 'one_channel' / 'default'; WURM_OBS_PARTIAL (+ NW) / WURM_OBS_NONE
+// OBSK: LANE_OBS_GRID1 / LANE_OBS_GRID3 ('one_channel' / 'default', lane_planes.hpp); WURM_OBS_PARTIAL (+ NW) / WURM_OBS_NONE
 constexpr int LW_TAB = 8192;                        // workgroup tables: 256 x float4, then 256 x float4 or the window masks
 constexpr int LW_VS = 128;                          // bytes per env of the value -> cell table
 constexpr int LW_QCAP = 128;                        // entries of lane_load_block's queue of non-zero float4s (20 bytes each)
@@ -54,14 +57,12 @@ struct LwGeo {
 
 // floats per env of the observation / interleaved bit planes of its flat strings
 template <int S, int OBSK, int NW>
-constexpr int lw_elems() { return OBSK == LW_OBS_GRID1 ? S * S : OBSK == LW_OBS_GRID3 ? 3 * S * S : OBSK == WURM_OBS_PARTIAL ? 3 * NW * NW : 0; } // (bit-plane modes)
-template <int OBSK>
-constexpr int lw_planes() { return OBSK == LW_OBS_GRID1 ? 4 : 2; }
+constexpr int lw_elems() { return OBSK == LANE_OBS_GRID1 ? S * S : OBSK == LANE_OBS_GRID3 ? 3 * S * S : OBSK == WURM_OBS_PARTIAL ? 3 * NW * NW : 0; } // (bit-plane modes)
 
 // per-wave LDS (bytes)
 template <int EPW, int S, int OBSK, int NW>
 struct LwLds {
-    static constexpr int E = lw_elems<S, OBSK, NW>(), NPL = lw_planes<OBSK>();
+    static constexpr int E = lw_elems<S, OBSK, NW>(), NPL = lane_plane_count<OBSK>();
     static constexpr int IO0 = 0;                          // uint4 [64] step inputs of pair (s, e), then the occupancy of its stepped state
     static constexpr int IO1 = IO0 + 1024;                 // uint2 [64] the rest of the record
     static constexpr int SCR = IO1 + 512;                  // flat bit strings of a chunk; start / end of launch scratch
@@ -172,24 +173,6 @@ __device__ __forceinline__ void lw_transition(u64 &o0, u64 &o1, u64 &qa, u64 &qb
     }
 }
 
-// tables of the bit-plane writers: tabA[low nibble: "value is 1", high nibble: "value is 127/255"]; for 'one_channel'
-// tabA[low nibble: 0.5, high: 1.0], tabB[low nibble: 1.5, high: -1.0] (the planes exclude each other: the sum is exact)
-template <int OBSK>
-__device__ __forceinline__ void lw_build_tables(float4 *tabA, float4 *tabB)
-{
-    for (int i = (int)threadIdx.x; i < 256; i += (int)blockDim.x) {
-        float a[4], b[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const bool lo = ((i >> j) & 1) != 0, hi = ((i >> (4 + j)) & 1) != 0;
-            if (OBSK == LW_OBS_GRID1) { a[j] = lo ? 0.5f : hi ? 1.0f : 0.0f; b[j] = lo ? 1.5f : hi ? -1.0f : 0.0f; }
-            else { a[j] = lo ? 1.0f : hi ? 127.0f / 255.0f : 0.0f; b[j] = 0.0f; }
-        }
-        tabA[i] = make_float4(a[0], a[1], a[2], a[3]);
-        if (OBSK == LW_OBS_GRID1) tabB[i] = make_float4(b[0], b[1], b[2], b[3]);
-    }
-}
-
 // wint[head cell] = the cells of the NW x NW window around it (bit NW i + j) that lie inside the border ring
 template <int S, int NW>
 __device__ __forceinline__ void lw_build_wint(u64 *wint)
@@ -220,18 +203,6 @@ __device__ __forceinline__ void lw_or128(u32 *bits, int k, int off, u64 v0, u64 
     if (d4) atomicOr(&P[4 * NPL], d4);
 }
 
-// ... a value of at most 64 bits (the crops: 25 / 49 bits per channel)
-template <int NPL>
-__device__ __forceinline__ void lw_or64(u32 *bits, int k, int off, u64 v)
-{
-    const int w = off >> 5, sb = off & 31;
-    const u64 a = (u64)(u32)v << sb, b = (u64)(u32)(v >> 32) << sb;
-    u32 *P = bits + NPL * w + k;
-    atomicOr(&P[0], (u32)a);
-    atomicOr(&P[NPL], (u32)(a >> 32) | (u32)b);
-    if ((u32)(b >> 32)) atomicOr(&P[2 * NPL], (u32)(b >> 32));
-}
-
 // the planes of pair `pair` of a stepped state: occupancy (o1:o0), head cell hc — also when it is on the ring —, food cell
 // fc (-1: none)
 template <int S, int OBSK, int NW>
@@ -243,13 +214,13 @@ __device__ __forceinline__ void lw_planes_of(u32 *bits, const u64 *wint, int pai
     lw_set(h0, h1, hc);
     h0 &= G::INT0; h1 &= G::INT1;                         // a head on the ring shows the ring
     if (fc >= 0) lw_set(f0, f1, fc);
-    if constexpr (OBSK == LW_OBS_GRID1) {
+    if constexpr (OBSK == LANE_OBS_GRID1) {
         const int off = C * pair;
         lw_or128<4>(bits, 0, off, o0 & G::INT0 & ~h0, o1 & G::INT1 & ~h1); // body without the head: 0.5
         lw_or128<4>(bits, 1, off, h0, h1);                                   // head: 1.0
         lw_or128<4>(bits, 2, off, f0, f1);                                   // food: 1.5
         lw_or128<4>(bits, 3, off, G::RING0, G::RING1);                       // ring: -1
-    } else if constexpr (OBSK == LW_OBS_GRID3) {
+    } else if constexpr (OBSK == LANE_OBS_GRID3) {
         const int off = 3 * C * pair;
         const u64 fr0 = G::INT0 & ~o0 & ~f0, fr1 = G::INT1 & ~o1 & ~f1;
         lw_or128<2>(bits, 0, off, fr0 | f0, fr1 | f1);                       // R: free or food
@@ -257,8 +228,7 @@ __device__ __forceinline__ void lw_planes_of(u32 *bits, const u64 *wint, int pai
         lw_or128<2>(bits, 0, off + 2 * C, fr0, fr1);                         // B: free
         lw_or128<2>(bits, 1, off + C, o0 & G::INT0 & ~h0, o1 & G::INT1 & ~h1); // G = 127/255: body
     } else if constexpr (OBSK == WURM_OBS_PARTIAL) {
-        // crop of the stepped state (:166-193): a window cell that is off the grid or on the ring is (0,0,0); food (1,0,0),
-        // head (0,1,0), body (0,127/255,0), background (1,1,1)
+        // crop of the stepped state (:166-193; the colours: lane_crop_colours)
         constexpr int n = NW / 2, W2 = NW * NW;
         const int hy = hc / S, hx = hc - hy * S;
         u64 V = 0;                                        // occupancy of the window, bit NW i + j
@@ -268,44 +238,13 @@ __device__ __forceinline__ void lw_planes_of(u32 *bits, const u64 *wint, int pai
         const int fy = fc >= 0 ? fc / S : -99, fx = fc - fy * S;
         const int wy = fy - (hy - n), wx = fx - (hx - n);
         const u64 F = (fc >= 0 && (unsigned)wy < (unsigned)NW && (unsigned)wx < (unsigned)NW) ? (1ull << (NW * wy + wx)) & W : 0ull;
-        const u64 R = W & ~V;                             // free or food: red
-        const u64 B = R & ~F;                             // free: blue (and green)
-        const u64 CENTRE = 1ull << (NW * n + n);
-        const u64 G1 = B | (W & CENTRE);                  // green 1: free, or the head inside the ring
-        const u64 GH = V & W & ~CENTRE;                   // green 127/255: body
+        const LaneCrop k = lane_crop_colours(V, W, F, 1ull << (NW * n + n));
         const int off = 3 * W2 * pair;
-        lw_or64<2>(bits, 0, off, R);
-        lw_or64<2>(bits, 0, off + W2, G1);
-        lw_or64<2>(bits, 0, off + 2 * W2, B);
-        lw_or64<2>(bits, 1, off + W2, GH);
+        lane_or64<2>(bits, 0, off, k.R);
+        lane_or64<2>(bits, 0, off + W2, k.G1);
+        lane_or64<2>(bits, 0, off + 2 * W2, k.B);
+        lane_or64<2>(bits, 1, off + W2, k.GH);
     }
-}
-
-// 16-byte group j of the flat run of floats whose bits start at bit 0 of the strings -> four floats
-template <int OBSK>
-__device__ __forceinline__ float4 lw_group(const u32 *bits, const float4 *tabA, const float4 *tabB, int j)
-{
-    const int w = j >> 3, sh = (j & 7) * 4;
-    if (OBSK == LW_OBS_GRID1) {
-        const uint4 q = ((const uint4 *)bits)[w];
-        const float4 a = tabA[((q.x >> sh) & 15u) | (((q.y >> sh) & 15u) << 4)];
-        const float4 b = tabB[((q.z >> sh) & 15u) | (((q.w >> sh) & 15u) << 4)];
-        return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
-    }
-    const uint2 q = ((const uint2 *)bits)[w];
-    return tabA[((q.x >> sh) & 15u) | (((q.y >> sh) & 15u) << 4)];
-}
-
-// float f of the flat run, bit by bit (the ragged last wave, the last chunk of a tape that is not a multiple of TC)
-template <int OBSK>
-__device__ __forceinline__ float lw_float(const u32 *bits, int f)
-{
-    constexpr int NPL = lw_planes<OBSK>();
-    const u32 *P = bits + NPL * (f >> 5);
-    const int b = f & 31;
-    if (OBSK == LW_OBS_GRID1)
-        return ((P[0] >> b) & 1u) ? 0.5f : ((P[1] >> b) & 1u) ? 1.0f : ((P[2] >> b) & 1u) ? 1.5f : ((P[3] >> b) & 1u) ? -1.0f : 0.0f;
-    return ((P[0] >> b) & 1u) ? 1.0f : ((P[1] >> b) & 1u) ? 127.0f / 255.0f : 0.0f;
 }
 
 // The state of a block of EPW consecutive envs, read cooperatively (lane_load_block for a whole aligned block, else three
@@ -420,7 +359,7 @@ __global__ __launch_bounds__(256) void lane_wide_rollout_kernel(StepArgs p)
     typedef LwGeo<S> G;
     static_assert(EPW == 8 || EPW == 16 || EPW == 32, "envs per wave");
     static_assert(S == 10 || S == 11, "grid size");
-    static_assert(OBSK == WURM_OBS_PARTIAL || OBSK == WURM_OBS_NONE || OBSK == LW_OBS_GRID1 || OBSK == LW_OBS_GRID3 ||
+    static_assert(OBSK == WURM_OBS_PARTIAL || OBSK == WURM_OBS_NONE || OBSK == LANE_OBS_GRID1 || OBSK == LANE_OBS_GRID3 ||
                   OBSK == WURM_OBS_POSITIONS, "observation");
     constexpr bool OBS = OBSK != WURM_OBS_NONE && OBSK != WURM_OBS_POSITIONS; // through bit planes
     constexpr bool POS = OBSK == WURM_OBS_POSITIONS;                          // four floats per pair, straight from its lane
@@ -434,7 +373,7 @@ __global__ __launch_bounds__(256) void lane_wide_rollout_kernel(StepArgs p)
     // ---- workgroup tables
     float4 *tab = (float4 *)lw_lds, *tabB = (float4 *)(lw_lds + 4096);
     u64 *wint = (u64 *)(lw_lds + 4096);           // (crops: in the place of 'one_channel's second table)
-    if (OBS) lw_build_tables<OBSK>(tab, tabB);
+    if (OBS) lane_build_tables<OBSK>(tab, tabB);
     if (OBSK == WURM_OBS_PARTIAL) lw_build_wint<S, NW>(wint);
     __syncthreads();
 
@@ -559,13 +498,7 @@ __global__ __launch_bounds__(256) void lane_wide_rollout_kernel(StepArgs p)
             // (3) pair lanes: outputs of (t, env) and its observation as bit planes
             {
                 const bool valid = pv && (rw & 0x8000u) != 0;
-                if (valid) {
-                    store_action(p.actions, p.act_dtype, oi, (long long)(int)(signed char)(rz >> 8));
-                    p.reward[oi] = (rw & 0x100u) ? 1.0f : 0.0f;
-                    p.done[oi] = (uint8_t)((rw & 0x600u) != 0);
-                    p.selfc[oi] = (uint8_t)((rw >> 9) & 1u);
-                    p.edgec[oi] = (uint8_t)((rw >> 10) & 1u);
-                }
+                if (valid) store_pair_outputs(p, oi, rz, rw);
                 if (OBS && valid) {
                     const int cp = (int)(rz & 127u), ai = (int)((rz >> 8) & 3u);
                     lw_planes_of<S, OBSK, NW>(bits, wint, lane, r0, r1, cp + lw_dcell<S>(ai), (int)(rw & 0xffu) - 1);
@@ -589,13 +522,13 @@ __global__ __launch_bounds__(256) void lane_wide_rollout_kernel(StepArgs p)
 #pragma unroll
                     for (int s = 0; s < TC; ++s, ob += step_f4) {
 #pragma unroll 4
-                        for (int g = lane; g < GSG; g += 64) ob[g] = lw_group<OBSK>(bits, tab, tabB, s * GSG + g);
+                        for (int g = lane; g < GSG; g += 64) ob[g] = lane_group<OBSK>(bits, tab, tabB, s * GSG + g);
                     }
                 } else { // the ragged last wave, the last chunk of a tape that is not a multiple of TC: float by float
                     for (int f = lane; f < 64 * E; f += 64) {
                         const int pr = f / E, k2 = f - pr * E, s = pr >> LOG_EPW, e = pr & (EPW - 1);
                         if (s < nt && e < nenv && (io1[pr].y & 0x8000u))
-                            obs_c[(long long)s * p.N * E + e * E + k2] = lw_float<OBSK>(bits, f);
+                            obs_c[(long long)s * p.N * E + e * E + k2] = lane_float<OBSK>(bits, f);
                     }
                 }
                 wave_lds_sync(); // (the next chunk's inputs go into io0)
@@ -667,15 +600,8 @@ static hipError_t launch_lane_wide_obs(const StepArgs &p, hipStream_t stream)
     // per 32 steps, default 0.323 against 0.303 per 16 — unlike lane_rollout.hpp's after its round-6 sweep: profiles/r06_lane_epw.txt)
     if (!(epw == 8 || epw == 16 || epw == 32)) epw = p.N >= 40960 ? 32 : p.N >= 12288 ? 16 : 8;
     if (inj) epw = 16;
-    const long long waves = (p.N + epw - 1) / epw;
-    const int wpb = waves >= 2048 ? 4 : 1;
-    dim3 block(64 * wpb), grid((unsigned)((waves + wpb - 1) / wpb));
     (void)hipGetLastError();
-    auto go = [&](auto kernel, int lds_per_wave) {
-        const size_t lds_bytes = (size_t)(LW_TAB + lds_per_wave * wpb);
-        if (lds_bytes > 65536) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        WURM_LAUNCH(kernel, grid, block, lds_bytes, stream, p);
-    };
+    auto go = [&](auto kernel, int lds_per_wave) { lane_launch(kernel, p, p.N, epw, 2048, LW_TAB, lds_per_wave, stream); };
     if (inj) go(lane_wide_rollout_kernel<16, S, OBSK, NW, true>, LwLds<16, S, OBSK, NW>::BYTES);
     else if (epw == 8) go(lane_wide_rollout_kernel<8, S, OBSK, NW, false>, LwLds<8, S, OBSK, NW>::BYTES);
     else if (epw == 16) go(lane_wide_rollout_kernel<16, S, OBSK, NW, false>, LwLds<16, S, OBSK, NW>::BYTES);
@@ -689,9 +615,9 @@ static hipError_t launch_lane_wide_size(const StepArgs &p, hipStream_t stream)
     if (p.obs_mode == WURM_OBS_NONE) return launch_lane_wide_obs<S, WURM_OBS_NONE, 0>(p, stream);
     if (p.obs_mode == WURM_OBS_PARTIAL && p.obs_n == 2) return launch_lane_wide_obs<S, WURM_OBS_PARTIAL, 5>(p, stream);
     if (p.obs_mode == WURM_OBS_PARTIAL && p.obs_n == 3) return launch_lane_wide_obs<S, WURM_OBS_PARTIAL, 7>(p, stream);
-    if (p.obs_mode == WURM_OBS_ONE_CHANNEL) return launch_lane_wide_obs<S, LW_OBS_GRID1, 0>(p, stream);
+    if (p.obs_mode == WURM_OBS_ONE_CHANNEL) return launch_lane_wide_obs<S, LANE_OBS_GRID1, 0>(p, stream);
     if (p.obs_mode == WURM_OBS_POSITIONS) return launch_lane_wide_obs<S, WURM_OBS_POSITIONS, 0>(p, stream);
-    return launch_lane_wide_obs<S, LW_OBS_GRID3, 0>(p, stream);
+    return launch_lane_wide_obs<S, LANE_OBS_GRID3, 0>(p, stream);
 }
 
 hipError_t launch_lane_wide(const StepArgs &p, hipStream_t stream)

@@ -15,7 +15,8 @@
 // without a mirror, as before — the entry point reports the mirror stale.
 // Contract: fused_step_kernel's without post_reset (deferred reset: envs flagged in p.done_in are rebuilt in front of the step
 // with call = p.pre_call); `obs` of the stepped state and, when asked for, `obs_after` of the state once the finished envs are
-// rebuilt with call + 1, as (which, env) pair lanes -> bit planes -> table -> 16-byte stores (lane_wide.hpp phases 3 and 4).
+// rebuilt with call + 1, as (which, env) pair lanes -> bit planes -> table -> 16-byte stores (lane_wide.hpp phases 3 and 4,
+// lane_planes.hpp).
 // Domain: lane_wide.hpp's, RNG mode.  An env outside it — or one that finished and is stepped again without the reset — is
 // stepped by fused_step_env (the one-env-per-wave code) on `envs` inside the same launch, and stays there until it is rebuilt.
 // Follows single_snake.py:197-304 (step), :322-387 (reset), :130-195 (_observe) like the kernels it stands in for.
@@ -159,7 +160,7 @@ __global__ __launch_bounds__(256) void lane_wide_resident_step_kernel(WideResArg
 
     float4 *tab = (float4 *)lwr_lds, *tabB = (float4 *)(lwr_lds + 4096);
     u64 *wint = (u64 *)(lwr_lds + 4096);
-    if (OBS) lw_build_tables<OBSK>(tab, tabB);
+    if (OBS) lane_build_tables<OBSK>(tab, tabB);
     if (OBSK == WURM_OBS_PARTIAL) lw_build_wint<S, NW>(wint);
     __syncthreads();
 
@@ -285,14 +286,14 @@ __global__ __launch_bounds__(256) void lane_wide_resident_step_kernel(WideResArg
                 constexpr int GSG = EPW * E / 4;   // 16-byte groups of one observation of the wave's envs
 #pragma unroll 4
                 for (int j = lane; j < NOBS * GSG; j += 64) {
-                    const float4 v = lw_group<OBSK>(bits, tab, tabB, j);
+                    const float4 v = lane_group<OBSK>(bits, tab, tabB, j);
                     const bool second = NOBS == 2 && j >= GSG;
                     ((float4 *)(second ? ob1 : ob0))[second ? j - GSG : j] = v;
                 }
             } else { // the ragged last wave: float by float
                 for (int f = lane; f < NP * E; f += 64) {
                     const int pr = f / E, k2 = f - pr * E, w = pr >> LOG_EPW, e = pr & (EPW - 1);
-                    if (e < nenv && (io1[pr].x & 0x100u)) (w ? ob1 : ob0)[e * E + k2] = lw_float<OBSK>(bits, f);
+                    if (e < nenv && (io1[pr].x & 0x100u)) (w ? ob1 : ob0)[e * E + k2] = lane_float<OBSK>(bits, f);
                 }
             }
         }
@@ -340,11 +341,8 @@ static hipError_t launch_lane_wide_resident_flush_size(const StepArgs &p, void *
     a.res = (uint4 *)resident;
     a.check_mask = nullptr;
     constexpr int EPW = 16;
-    const long long waves = (p.N + EPW - 1) / EPW;
-    const int wpb = waves >= 1024 ? 4 : 1;
-    dim3 block(64 * wpb), grid((unsigned)((waves + wpb - 1) / wpb));
     (void)hipGetLastError();
-    WURM_LAUNCH((lane_wide_resident_flush_kernel<EPW, S>), grid, block, (size_t)((EPW * LwGeo<S>::BM + 4 * EPW) * wpb), stream, a);
+    lane_launch(lane_wide_resident_flush_kernel<EPW, S>, a, p.N, EPW, 1024, 0, EPW * LwGeo<S>::BM + 4 * EPW, stream);
     return hipGetLastError();
 }
 
@@ -361,24 +359,16 @@ static hipError_t launch_lane_wide_resident_obs(const WideResArgs &a, hipStream_
     // envs per wave (automatic unless the option WURM_RESIDENT_EPW forces it: tests and the tuning sweep)
     int epw = (int)opt.resident_epw;
     if (epw != 16 && epw != 32) epw = nobs == 1 ? (p.N >= 16384 ? 32 : 16) : (p.N >= 49152 ? 32 : 16);
-    auto go = [&](auto kernel, int e, int wave_bytes) {
-        const long long waves = (p.N + e - 1) / e;
-        const int wpb = waves >= 1024 ? 4 : 1;
-        dim3 block(64 * wpb), grid((unsigned)((waves + wpb - 1) / wpb));
-        const size_t lds_bytes = (size_t)(LW_TAB + wave_bytes * wpb);
-        if (lds_bytes > 65536) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        WURM_LAUNCH(kernel, grid, block, lds_bytes, stream, a);
-    };
-    if constexpr (OBSK == WURM_OBS_NONE) {
-        if (epw == 16) go(lane_wide_resident_step_kernel<16, S, OBSK, NW, 1>, 16, lwr_wave_bytes<16, S, OBSK, NW>());
-        else go(lane_wide_resident_step_kernel<32, S, OBSK, NW, 1>, 32, lwr_wave_bytes<32, S, OBSK, NW>());
-    } else if (nobs == 2) {
-        if (epw == 16) go(lane_wide_resident_step_kernel<16, S, OBSK, NW, 2>, 16, lwr_wave_bytes<16, S, OBSK, NW>());
-        else go(lane_wide_resident_step_kernel<32, S, OBSK, NW, 2>, 32, lwr_wave_bytes<32, S, OBSK, NW>());
-    } else {
-        if (epw == 16) go(lane_wide_resident_step_kernel<16, S, OBSK, NW, 1>, 16, lwr_wave_bytes<16, S, OBSK, NW>());
-        else go(lane_wide_resident_step_kernel<32, S, OBSK, NW, 1>, 32, lwr_wave_bytes<32, S, OBSK, NW>());
+    auto go = [&](auto kernel, int e, int wave_bytes) { lane_launch(kernel, a, p.N, e, 1024, LW_TAB, wave_bytes, stream); };
+    if constexpr (OBSK != WURM_OBS_NONE) { // (without an observation nobs is 1, and there is no NOBS = 2 kernel)
+        if (nobs == 2) {
+            if (epw == 16) go(lane_wide_resident_step_kernel<16, S, OBSK, NW, 2>, 16, lwr_wave_bytes<16, S, OBSK, NW>());
+            else go(lane_wide_resident_step_kernel<32, S, OBSK, NW, 2>, 32, lwr_wave_bytes<32, S, OBSK, NW>());
+            return hipGetLastError();
+        }
     }
+    if (epw == 16) go(lane_wide_resident_step_kernel<16, S, OBSK, NW, 1>, 16, lwr_wave_bytes<16, S, OBSK, NW>());
+    else go(lane_wide_resident_step_kernel<32, S, OBSK, NW, 1>, 32, lwr_wave_bytes<32, S, OBSK, NW>());
     return hipGetLastError();
 }
 
@@ -392,19 +382,16 @@ static hipError_t launch_lane_wide_resident_size(const StepArgs &p, void *reside
     (void)hipGetLastError();
     if (!valid) {
         constexpr int EPW = 16;
-        const long long waves = (p.N + EPW - 1) / EPW;
-        const int wpb = waves >= 1024 ? 4 : 1;
-        dim3 block(64 * wpb), grid((unsigned)((waves + wpb - 1) / wpb));
-        WURM_LAUNCH((lane_wide_resident_build_kernel<EPW, S>), grid, block, (size_t)(LwLds<EPW, S, WURM_OBS_NONE, 0>::BYTES * wpb), stream, a);
+        lane_launch(lane_wide_resident_build_kernel<EPW, S>, a, p.N, EPW, 1024, 0, LwLds<EPW, S, WURM_OBS_NONE, 0>::BYTES, stream);
         hipError_t err = hipGetLastError();
         if (err != hipSuccess) return err;
     }
     if (p.obs_mode == WURM_OBS_NONE) return launch_lane_wide_resident_obs<S, WURM_OBS_NONE, 0>(a, stream);
     if (p.obs_mode == WURM_OBS_PARTIAL && p.obs_n == 2) return launch_lane_wide_resident_obs<S, WURM_OBS_PARTIAL, 5>(a, stream);
     if (p.obs_mode == WURM_OBS_PARTIAL && p.obs_n == 3) return launch_lane_wide_resident_obs<S, WURM_OBS_PARTIAL, 7>(a, stream);
-    if (p.obs_mode == WURM_OBS_ONE_CHANNEL) return launch_lane_wide_resident_obs<S, LW_OBS_GRID1, 0>(a, stream);
+    if (p.obs_mode == WURM_OBS_ONE_CHANNEL) return launch_lane_wide_resident_obs<S, LANE_OBS_GRID1, 0>(a, stream);
     if (p.obs_mode == WURM_OBS_POSITIONS) return launch_lane_wide_resident_obs<S, WURM_OBS_POSITIONS, 0>(a, stream);
-    return launch_lane_wide_resident_obs<S, LW_OBS_GRID3, 0>(a, stream);
+    return launch_lane_wide_resident_obs<S, LANE_OBS_GRID3, 0>(a, stream);
 }
 
 // (lazy form only: see the header of this file)

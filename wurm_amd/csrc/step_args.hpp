@@ -51,6 +51,17 @@ __device__ __forceinline__ void store_action(void *actions, int dtype, long long
     else ((int *)actions)[i] = (int)v;
 }
 
+// The per-step outputs of pair oi = t N + env of a lane rollout (lane_rollout.hpp, lane_wide.hpp) from the record of its
+// stepped state: rz = . | sanitised action << 8, rw = . | ate << 8 | self collision << 9 | edge collision << 10
+__device__ __forceinline__ void store_pair_outputs(const StepArgs &p, long long oi, u32 rz, u32 rw)
+{
+    store_action(p.actions, p.act_dtype, oi, (long long)(int)(signed char)(rz >> 8));
+    p.reward[oi] = (rw & 0x100u) ? 1.0f : 0.0f;
+    p.done[oi] = (uint8_t)((rw & 0x600u) != 0);
+    p.selfc[oi] = (uint8_t)((rw >> 9) & 1u);
+    p.edgec[oi] = (uint8_t)((rw >> 10) & 1u);
+}
+
 // LDS-resident clock-grid rollout (grid_rollout.hip): true if it took the launch (SingleSnake, S >= 12).  Envs whose
 // state is outside its domain are left untouched and marked with done[0][env] = GRID_SKIPPED for the generic kernel.
 constexpr uint8_t GRID_SKIPPED = 0xFF;

@@ -402,6 +402,74 @@ def test_hand_made_states_refuse_the_mirror(hip):
             prev = ro['done']
 
 
+def test_abi_a_call_the_mirror_does_not_serve_writes_a_lazy_mirror_out(hip):
+    """wurm_grid_step_reset: three `step; postponed reset` calls on a LAZY mirror (the planes see the first, which builds it,
+    and no other), then a call the lane kernel does not serve (post_reset) — fused_entry has to write the records out to the
+    planes before the one-env-per-wave kernel steps them, and report the mirror stale.  70 envs: one full wave of lanes and a
+    partial one.  Everything returned and the state against the oracle."""
+    from wurm_amd._lib import knobs
+    N, S, start, mode = 70, 9, (4, 4), 'default'
+    rng = np.random.RandomState(4)
+    o, h = OracleBackend(seed=23), hip(seed=23)
+    eo = _fresh(o, N, S, start)
+    eh = eo.copy()
+    res = {'lazy': True, 'sync': False}
+    prev = None
+    with knobs(WURM_LANE_STEP_MIN_ENVS=0):
+        for t in range(4):
+            a = rng.randint(0, 4, size=N).astype(np.int64)
+            kw = dict(call=1 + 2 * t, pre_done=prev, pre_call=2 * t, post_reset=(t == 3), grid=start)
+            ro = o.single_step_reset(eo, a.copy(), mode, **kw)
+            rh = h.single_step_reset(eh, a.copy(), mode, resident=res, **kw)
+            _cmp_step(ro, rh, t)
+            if t < 3:
+                assert res['valid'] == 1
+            if t == 2:   # (the device's planes: what the unserved call would step without the flush)
+                assert not np.array_equal(res['envs_dev'].cpu().numpy(), eo), 'the planes are current: nothing to write out'
+            prev = ro['done']
+    assert res['valid'] == 0
+    _same(eh, eo, 'state')
+
+
+def test_class_rollout_the_lane_kernel_does_not_serve_writes_a_lazy_mirror_out():
+    """SimpleGridworld.rollout of a batch below the lane ROLLOUT kernel's threshold, after three `step; reset` iterations on a
+    lazy valid mirror: wurm_grid_rollout_resident writes the mirror out, rolls out on the planes and reports it stale.
+    Everything returned and env.envs against the oracle."""
+    import torch
+    from oracle import oracle
+    from wurm_amd._lib import knobs
+    from wurm_amd.envs import SimpleGridworld
+    N, S, start, mode, seed = 70, 9, (4, 4), 'default', 29
+    acts = torch.randint(4, (6, N), generator=torch.Generator().manual_seed(5))
+    ref = np.zeros((N, 2, S, S), np.float32)
+    oracle.grid_reset(ref, np.ones(N, np.uint8), start, 'none', seed=seed, call=0)
+    with knobs(WURM_RESIDENT_MIN_ENVS=0, WURM_LANE_STEP_MIN_ENVS=0, WURM_LANE_ROLLOUT_MIN_ENVS=1 << 40):
+        env = SimpleGridworld(N, S, observation_mode=mode, start_location=start, device='cuda:0', seed=seed)
+        for t in range(3):
+            a, a_ref = acts[t].to('cuda:0'), acts[t].numpy().copy()
+            obs, r, d, info = env.step(a)
+            o_ref, r_ref, d_ref, ec_ref = oracle.grid_step(ref, a_ref, mode, seed=seed, call=1 + 2 * t)
+            _same(obs.cpu().numpy(), o_ref, f'obs t={t}')
+            _same(r.squeeze(-1).cpu().numpy(), r_ref, f'reward t={t}')
+            _same(d.squeeze(-1).cpu().numpy().astype(np.uint8), d_ref, f'done t={t}')
+            _same(info['edge_collision'].cpu().numpy().astype(np.uint8), ec_ref, f'edge_collision t={t}')
+            env.reset(d, return_observations=False)
+            oracle.grid_reset(ref, d_ref, start, 'none', seed=seed, call=2 + 2 * t)
+        assert env._c.resident_valid == 1 and env._c.resident_lazy == 1
+        a, a_ref = acts[3:].to('cuda:0').contiguous(), acts[3:].numpy().copy()
+        out = env.rollout(a)
+        assert _route() == 'generic'
+        exp = oracle.grid_rollout(ref, a_ref, start, mode, seed=seed, call0=7)
+        assert env._c.resident_valid == 0
+    assert list(out) == ['observations', 'rewards', 'dones', 'edge_collision']
+    _same(a.cpu().numpy(), a_ref, 'actions')
+    _same(out['observations'].cpu().numpy(), exp['obs'], 'observations')
+    _same(out['rewards'].cpu().numpy(), exp['reward'], 'rewards')
+    _same(out['dones'].cpu().numpy().astype(np.uint8), exp['done'], 'dones')
+    _same(out['edge_collision'].cpu().numpy().astype(np.uint8), exp['edge_collision'], 'edge_collision')
+    _same(env.envs.cpu().numpy(), ref, 'state')
+
+
 def test_class_loop_on_the_mirror():
     """SimpleGridworld(16 384 envs) through `env.step(a); env.reset(done)`: ONE launch per iteration on the mirror
     (mirror_state: lazy, current), equal outputs and state to the same loop with resident_mirror=False; a look at the state

@@ -268,6 +268,81 @@ def test_host_mirror_stays_current_in_the_plain_loop():
         assert env._c.resident_valid == 1
 
 
+def test_a_rollout_after_lazy_steps_writes_the_mirror_out():
+    """SingleSnake.rollout at 9 x 9 runs on the planes: after three `step; reset` iterations on a LAZY valid mirror (the planes
+    have seen none of them) wurm_single_rollout_resident has to write the mirror out first — the 9 x 9 arm of the library's
+    "this call cannot use the mirror" ladder.  70 envs: a full wave of lanes and a partial one.  Everything against the oracle."""
+    import torch
+    from oracle import oracle
+    N, S, seed, mode = 70, 9, 31, 'partial_2'
+    acts = torch.randint(4, (6, N), generator=torch.Generator().manual_seed(3))
+    ref = np.zeros((N, 3, S, S), np.float32)
+    oracle.single_reset(ref, np.ones(N, np.uint8), 'none', seed=seed, call=0)
+    with knobs(WURM_RESIDENT_MIN_ENVS=0):
+        env = _make(N, mode, seed=seed)
+        for t in range(3):
+            a, a_ref = acts[t].to('cuda:0'), acts[t].numpy().copy()
+            obs, r, d, info = env.step(a)
+            o_ref, r_ref, d_ref, sc_ref, ec_ref = oracle.single_step(ref, a_ref, mode, seed=seed, call=1 + 2 * t)
+            _same(a.cpu().numpy(), a_ref, f'sanitised actions t={t}')
+            _same(obs.cpu().numpy(), o_ref, f'obs t={t}')
+            _same(r.squeeze(-1).cpu().numpy(), r_ref, f'reward t={t}')
+            _same(d.squeeze(-1).cpu().numpy().astype(np.uint8), d_ref, f'done t={t}')
+            _same(info['self_collision'].cpu().numpy().astype(np.uint8), sc_ref, f'self_collision t={t}')
+            _same(info['edge_collision'].cpu().numpy().astype(np.uint8), ec_ref, f'edge_collision t={t}')
+            env.reset(d, return_observations=False)
+            oracle.single_reset(ref, d_ref, 'none', seed=seed, call=2 + 2 * t)
+        assert env._c.resident_valid == 1 and env._c.resident_lazy == 1
+        a, a_ref = acts[3:].to('cuda:0').contiguous(), acts[3:].numpy().copy()
+        out = env.rollout(a)
+        exp = oracle.single_rollout(ref, a_ref, mode, seed=seed, call0=7)
+        assert env._c.resident_valid == 0                     # (the rollout wrote the planes: the mirror is stale)
+    _same(a.cpu().numpy(), a_ref, 'sanitised actions')
+    assert list(out) == ['observations', 'rewards', 'dones', 'self_collision', 'edge_collision']
+    _same(out['observations'].cpu().numpy(), exp['obs'], 'observations')
+    _same(out['rewards'].cpu().numpy(), exp['reward'], 'rewards')
+    for k, ko in (('dones', 'done'), ('self_collision', 'self_collision'), ('edge_collision', 'edge_collision')):
+        _same(out[k].cpu().numpy().astype(np.uint8), exp[ko], k)
+    _same(env.envs.cpu().numpy(), ref, 'state')
+
+
+def unserved_call_on_a_lazy_mirror(hip, S, N, mode):
+    """wurm_single_step_reset through the C ABI: three `step; postponed reset` calls on a LAZY mirror (the planes see none of
+    them), then a call the mirror kernels do not serve (post_reset: the reset behind the step, in the same launch) — fused_entry
+    has to write the mirror out first, by the kernel of the family that keeps it at this size, and report it stale.
+    Everything the calls return, the sanitised actions and the state against the oracle."""
+    o, h = OracleBackend(seed=17, env_offset=3), hip(seed=17, env_offset=3)
+    eo = np.zeros((N, 3, S, S), np.float32)
+    o.single_reset(eo, np.ones(N, np.uint8), 'none')
+    eh = eo.copy()
+    rng = np.random.RandomState(S)
+    mirror = {'valid': 0, 'lazy': True, 'sync': False}
+    prev = None
+    with knobs(WURM_RESIDENT_MIN_ENVS=0):
+        for t in range(4):
+            a = rng.randint(0, 4, size=N).astype(np.int64)
+            ao, ah = a.copy(), a.copy()
+            kw = dict(call=1 + 2 * t, pre_done=prev, pre_call=2 * t, post_reset=(t == 3))
+            ro = o.single_step_reset(eo, ao, mode, **kw)
+            rh = h.single_step_reset(eh, ah, mode, resident=mirror, **kw)
+            _same(ah, ao, f'actions t={t}')
+            _cmp(ro, rh, t)
+            if t < 3:
+                assert mirror['valid'] == 1
+            if t == 2:   # (the device's planes: what the unserved call would step without the flush)
+                assert not np.array_equal(mirror['envs_dev'].cpu().numpy(), eo), 'the planes are current: nothing to write out'
+            prev = ro['done']
+    assert mirror['valid'] == 0
+    _same(eh, eo, 'state')
+
+
+@pytest.mark.parametrize('S,mode', [(9, 'partial_2'), (12, 'default'), (16, 'partial_2')])
+def test_abi_a_call_the_mirror_does_not_serve_writes_a_lazy_mirror_out(hip, S, mode):
+    """9 x 9 (lane_resident.hpp's flush) and 12 x 12 and larger (the clock grids', grid_rollout.hip); 70 envs: one full wave
+    of lanes and a partial one"""
+    unserved_call_on_a_lazy_mirror(hip, S, 70, mode)
+
+
 def test_inference_mode_state_tensor_cannot_be_watched():
     import torch
     with knobs(WURM_RESIDENT_MIN_ENVS=0):

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from tests.backends import OracleBackend
-from tests.test_lane_resident import _cmp, _same
+from tests.test_lane_resident import _cmp, _same, unserved_call_on_a_lazy_mirror
 
 pytestmark = pytest.mark.gpu
 
@@ -241,6 +241,12 @@ def test_check_masks_of_the_step_launch_equal_the_checker(hip):
         env.check_consistency(~d.squeeze(-1))
         env.reset(d, return_observations=False)
     env.check_consistency()
+
+
+@pytest.mark.parametrize('S,mode', [(10, 'partial_2'), (11, 'default')])
+def test_abi_a_call_the_mirror_does_not_serve_writes_a_lazy_mirror_out(hip, S, mode):
+    """fused_entry's 10 x 10 / 11 x 11 arm of "this call cannot use the mirror" (tests/test_lane_resident.py)"""
+    unserved_call_on_a_lazy_mirror(hip, S, 70, mode)
 
 
 @pytest.mark.parametrize('S,mode', [(10, 'default'), (11, 'partial_2')])

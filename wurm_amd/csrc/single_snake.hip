@@ -35,6 +35,96 @@ static int check_common(bool snake, const void *envs, long long N, int S, const 
     return WURM_OK;
 }
 
+// check_common, then the part of the argument block every entry point and fused_entry share
+static int checked_args(bool snake, StepArgs &p, float *envs, float *obs, int obs_mode, int obs_n, long long N, int S,
+                        int dtype, u64 seed, u64 call, long long env_offset)
+{
+    p = {};
+    p.envs = envs; p.obs = obs; p.obs_mode = obs_mode; p.obs_n = obs_n; p.obs_elems = obs_elems(snake, obs_mode, obs_n, S);
+    p.N = N; p.S = S; p.seed = seed; p.call = call; p.env_offset = env_offset;
+    return check_common(snake, envs, N, S, obs, obs_mode, obs_n, dtype);
+}
+
+// ... and the per-step outputs (SimpleGridworld has no self collision: selfc is null)
+static void step_outputs(StepArgs &p, const void *actions, int dtype, float *reward, uint8_t *done, uint8_t *selfc, uint8_t *edgec)
+{
+    p.actions = const_cast<void *>(actions); p.act_dtype = dtype; p.reward = reward; p.done = done; p.selfc = selfc; p.edgec = edgec;
+}
+
+static bool start_ok(int size, int y, int x) { return y >= 0 && x >= 0 && y < size && x < size; } // simple_gridworld.py:254-260
+
+// The validation of the four rollout entry points, in the order their callers see, and their argument block.  WURM_OK with
+// num_steps == 0 is "nothing to do"; the _resident forms have nothing to do at num_envs == 0 either, the plain ones leave that to launch.
+static int rollout_args(bool snake, StepArgs &p, float *envs, const void *actions, int dtype, float *reward, uint8_t *done,
+                        uint8_t *selfc, uint8_t *edgec, float *obs, int obs_mode, int obs_n, long long N, int S, long long T,
+                        int start_y, int start_x, u64 seed, u64 call0, long long env_offset)
+{
+    int rc = checked_args(snake, p, envs, obs, obs_mode, obs_n, N, S, dtype, seed, call0, env_offset);
+    if (rc) return rc;
+    if (T < 0) return WURM_ERR_INVALID_ARG;
+    if (S <= (snake ? 8 : 4)) return WURM_ERR_UNSUPPORTED;
+    if (!snake && !start_ok(S, start_y, start_x)) return WURM_ERR_UNSUPPORTED;
+    if (N > 0 && T > 0 && (!actions || !reward || !done || !edgec || (snake && !selfc))) return WURM_ERR_INVALID_ARG;
+    step_outputs(p, actions, dtype, reward, done, selfc, edgec);
+    p.T = T; p.start_y = start_y; p.start_x = start_x;
+    return WURM_OK;
+}
+
+static int launch_kind(bool snake, Kind kind, const StepArgs &p, void *stream)
+{
+    return snake ? launch<true>(kind, p, stream) : launch<false>(kind, p, stream);
+}
+
+// "This call cannot use the mirror" (and the flush entry points): a lazy valid mirror is written out to envs, by the kernel
+// of the family that keeps it.  WURM_ERR_INVALID_ARG: no SingleSnake mirror exists at this size (nothing was launched).
+static int write_out_lazy_mirror(bool snake, StepArgs p, void *resident, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t err;
+    p.resident = resident;
+    if (!snake) err = launch_gridworld_lane_flush(p, st);
+    else if (p.S == 9) err = launch_lane_resident_flush(p, resident, st);
+    else if (p.S == 10 || p.S == 11) err = launch_lane_wide_resident_flush(p, resident, st);
+    else if (grid_step_eligible(p)) err = launch_grid_resident_flush(p, st);
+    else return WURM_ERR_INVALID_ARG;
+    return err == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+}
+
+// A SimpleGridworld launch on the caller's mirror (gridworld_lane.hip; valid: 0 = build it in this launch, 1 = current).
+// *state: 1 = the mirror describes the state, 2 = refused, 0 = the launch failed; left alone if nothing was launched.
+// A launch that BUILT the mirror (and wrote the planes whatever `lazy` says) is valid only if it could describe every env:
+// one synchronous 4-byte read per build — the first launch of an env object, and the one after something else wrote the
+// state — is what lets every other call be a single launch.
+static int launch_gridworld_on_mirror(Kind kind, StepArgs p, void *resident, int valid, int lazy, void *stream, int *state)
+{
+    hipStream_t st = (hipStream_t)stream;
+    p.resident = resident;
+    p.resident_valid = valid == 1;
+    p.resident_lazy = lazy != 0;
+    if (!p.resident_valid && hipMemsetAsync(resident, 0, 16, st) != hipSuccess) return WURM_ERR_HIP;
+    const int rc = launch<false>(kind, p, stream);
+    if (rc != WURM_OK) { *state = 0; return rc; }
+    int odd = 0;
+    if (!p.resident_valid && (hipMemcpyAsync(&odd, resident, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                              hipStreamSynchronize(st) != hipSuccess))
+        return WURM_ERR_HIP;
+    *state = odd != 0 ? 2 : 1;
+    return WURM_OK;
+}
+
+// `go(kernel<CPL>)` for the cells per lane pick_cpl chose (the ladder of launch and of policy_wide.hpp)
+#define WURM_CPL_LADDER(cpl, go, kernel) \
+    switch (cpl) { \
+    case 2: go(kernel<2>); break; \
+    case 4: go(kernel<4>); break; \
+    case 8: go(kernel<8>); break; \
+    case 16: go(kernel<16>); break; \
+    case 24: go(kernel<24>); break; \
+    case 32: go(kernel<32>); break; \
+    case 48: go(kernel<48>); break; \
+    default: go(kernel<64>); break; \
+    }
+
 // policy_wide.hip: the fused actor beyond policy_rollout.hpp's domain, and the route of the last policy launch
 int launch_policy_wide(const PolicyArgs &p, int obs_mode, int obs_n, void *stream);
 extern thread_local int policy_route;
@@ -48,23 +138,15 @@ static int launch_policy_rollout(const PolicyArgs &p, int obs_n, void *stream)
     hipStream_t st = (hipStream_t)stream;
     (void)hipGetLastError();
     const bool s9 = p.S == 9 && !opt.policy_generic; // (debug switch: time / test the generic loop on 9x9 grids)
+    auto go = [&](auto s9_kernel, auto kernel) {
+        if (s9) WURM_LAUNCH(s9_kernel, grid, block, lds, st, p);
+        else WURM_LAUNCH(kernel, grid, block, lds, st, p);
+    };
     switch (obs_n) {
-    case 0:
-        if (s9) WURM_LAUNCH(policy_rollout_s9_kernel<0>, grid, block, lds, st, p);
-        else WURM_LAUNCH(policy_rollout_kernel<0>, grid, block, lds, st, p);
-        break;
-    case 1:
-        if (s9) WURM_LAUNCH(policy_rollout_s9_kernel<1>, grid, block, lds, st, p);
-        else WURM_LAUNCH(policy_rollout_kernel<1>, grid, block, lds, st, p);
-        break;
-    case 2:
-        if (s9) WURM_LAUNCH(policy_rollout_s9_kernel<2>, grid, block, lds, st, p);
-        else WURM_LAUNCH(policy_rollout_kernel<2>, grid, block, lds, st, p);
-        break;
-    case 3:
-        if (s9) WURM_LAUNCH(policy_rollout_s9_kernel<3>, grid, block, lds, st, p);
-        else WURM_LAUNCH(policy_rollout_kernel<3>, grid, block, lds, st, p);
-        break;
+    case 0: go(policy_rollout_s9_kernel<0>, policy_rollout_kernel<0>); break;
+    case 1: go(policy_rollout_s9_kernel<1>, policy_rollout_kernel<1>); break;
+    case 2: go(policy_rollout_s9_kernel<2>, policy_rollout_kernel<2>); break;
+    case 3: go(policy_rollout_s9_kernel<3>, policy_rollout_kernel<3>); break;
     default: return WURM_ERR_UNSUPPORTED;
     }
     return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
@@ -87,14 +169,12 @@ int wurm_single_step(float *envs, void *actions, int actions_dtype, float *rewar
                      int64_t num_envs, int size, uint64_t seed, uint64_t call, int64_t env_offset,
                      const int32_t *inject_food, void *stream)
 {
-    int rc = check_common(true, envs, num_envs, size, obs, obs_mode, obs_n, actions_dtype);
+    StepArgs p;
+    int rc = checked_args(true, p, envs, obs, obs_mode, obs_n, num_envs, size, actions_dtype, seed, call, env_offset);
     if (rc) return rc;
     if (num_envs > 0 && (!actions || !reward || !done || !self_collision || !edge_collision)) return WURM_ERR_INVALID_ARG;
-    StepArgs p = {};
-    p.envs = envs; p.actions = actions; p.act_dtype = actions_dtype; p.reward = reward; p.done = done;
-    p.selfc = self_collision; p.edgec = edge_collision; p.obs = obs; p.obs_mode = obs_mode; p.obs_n = obs_n;
-    p.obs_elems = obs_elems(true, obs_mode, obs_n, size); p.N = num_envs; p.S = size; p.seed = seed; p.call = call;
-    p.env_offset = env_offset; p.inject_food = inject_food;
+    step_outputs(p, actions, actions_dtype, reward, done, self_collision, edge_collision);
+    p.inject_food = inject_food;
     return launch<true>(K_STEP, p, stream);
 }
 
@@ -102,14 +182,12 @@ int wurm_single_reset(float *envs, const uint8_t *done, float *obs, int obs_mode
                       int size, uint64_t seed, uint64_t call, int64_t env_offset, const int32_t *inject_reset,
                       void *stream)
 {
-    int rc = check_common(true, envs, num_envs, size, obs, obs_mode, obs_n, WURM_ACT_I64);
+    StepArgs p;
+    int rc = checked_args(true, p, envs, obs, obs_mode, obs_n, num_envs, size, WURM_ACT_I64, seed, call, env_offset);
     if (rc) return rc;
     if (size <= 8) return WURM_ERR_UNSUPPORTED; // single_snake.py:346-347
     if (num_envs > 0 && !done) return WURM_ERR_INVALID_ARG;
-    StepArgs p = {};
-    p.envs = envs; p.done_in = done; p.obs = obs; p.obs_mode = obs_mode; p.obs_n = obs_n;
-    p.obs_elems = obs_elems(true, obs_mode, obs_n, size); p.N = num_envs; p.S = size; p.seed = seed; p.call = call;
-    p.env_offset = env_offset; p.inject_reset = inject_reset;
+    p.done_in = done; p.inject_reset = inject_reset;
     return launch<true>(K_RESET, p, stream);
 }
 
@@ -117,12 +195,9 @@ int wurm_single_observe(const float *envs, float *obs, int obs_mode, int obs_n, 
                         void *stream)
 {
     if (obs_mode == WURM_OBS_NONE) return WURM_ERR_INVALID_ARG;
-    int rc = check_common(true, envs, num_envs, size, obs, obs_mode, obs_n, WURM_ACT_I64);
-    if (rc) return rc;
-    StepArgs p = {};
-    p.envs = const_cast<float *>(envs); p.obs = obs; p.obs_mode = obs_mode; p.obs_n = obs_n;
-    p.obs_elems = obs_elems(true, obs_mode, obs_n, size); p.N = num_envs; p.S = size;
-    return launch<true>(K_OBSERVE, p, stream);
+    StepArgs p;
+    int rc = checked_args(true, p, const_cast<float *>(envs), obs, obs_mode, obs_n, num_envs, size, WURM_ACT_I64, 0, 0, 0);
+    return rc ? rc : launch<true>(K_OBSERVE, p, stream);
 }
 
 int wurm_single_rollout(float *envs, void *actions, int actions_dtype, float *reward, uint8_t *done,
@@ -130,18 +205,11 @@ int wurm_single_rollout(float *envs, void *actions, int actions_dtype, float *re
                         int64_t num_envs, int size, int64_t num_steps, uint64_t seed, uint64_t call0,
                         int64_t env_offset, const int32_t *inject_food, const int32_t *inject_reset, void *stream)
 {
-    int rc = check_common(true, envs, num_envs, size, obs, obs_mode, obs_n, actions_dtype);
-    if (rc) return rc;
-    if (num_steps < 0) return WURM_ERR_INVALID_ARG;
-    if (size <= 8) return WURM_ERR_UNSUPPORTED;
-    if (num_envs > 0 && num_steps > 0 && (!actions || !reward || !done || !self_collision || !edge_collision))
-        return WURM_ERR_INVALID_ARG;
-    if (num_steps == 0) return WURM_OK;
-    StepArgs p = {};
-    p.envs = envs; p.actions = actions; p.act_dtype = actions_dtype; p.reward = reward; p.done = done;
-    p.selfc = self_collision; p.edgec = edge_collision; p.obs = obs; p.obs_mode = obs_mode; p.obs_n = obs_n;
-    p.obs_elems = obs_elems(true, obs_mode, obs_n, size); p.N = num_envs; p.S = size; p.T = num_steps; p.seed = seed;
-    p.call = call0; p.env_offset = env_offset; p.inject_food = inject_food; p.inject_reset = inject_reset;
+    StepArgs p;
+    int rc = rollout_args(true, p, envs, actions, actions_dtype, reward, done, self_collision, edge_collision, obs, obs_mode,
+                          obs_n, num_envs, size, num_steps, 0, 0, seed, call0, env_offset);
+    if (rc || num_steps == 0) return rc;
+    p.inject_food = inject_food; p.inject_reset = inject_reset;
     return launch<true>(K_ROLLOUT, p, stream);
 }
 
@@ -149,9 +217,13 @@ int wurm_single_rollout(float *envs, void *actions, int actions_dtype, float *re
 // mirror is stale), -1 = nothing was launched
 static int fused_entry(bool snake, const wurm_single_call *c, void *stream, int *mirror_state = nullptr)
 {
-    if (mirror_state) *mirror_state = -1;
+    int unused;
+    int &mirror = mirror_state ? *mirror_state : unused;
+    mirror = -1;
     if (!c) return WURM_ERR_INVALID_ARG;
-    int rc = check_common(snake, c->envs, c->num_envs, c->size, c->obs, c->obs_mode, c->obs_n, c->actions_dtype);
+    StepArgs p;
+    int rc = checked_args(snake, p, c->envs, c->obs, c->obs_mode, c->obs_n, c->num_envs, c->size, c->actions_dtype, c->seed,
+                          c->call, c->env_offset);
     if (rc) return rc;
     const int64_t N = c->num_envs;
     if (N > 0 && (!c->actions || !c->reward || !c->done || !c->edge_collision || (snake && !c->self_collision)))
@@ -159,23 +231,22 @@ static int fused_entry(bool snake, const wurm_single_call *c, void *stream, int 
     const bool resets = c->pre_done || c->post_reset || c->obs_after;
     if (resets) { // the same limits as wurm_single_reset / wurm_grid_reset
         if (snake && c->size <= 8) return WURM_ERR_UNSUPPORTED;
-        if (!snake && (c->size <= 4 || c->start_y < 0 || c->start_x < 0 || c->start_y >= c->size || c->start_x >= c->size))
-            return WURM_ERR_UNSUPPORTED;
+        if (!snake && (c->size <= 4 || !start_ok(c->size, c->start_y, c->start_x))) return WURM_ERR_UNSUPPORTED;
     }
-    StepArgs p = {};
-    p.envs = c->envs; p.actions = c->actions; p.act_dtype = c->actions_dtype; p.reward = c->reward; p.done = c->done;
-    p.selfc = c->self_collision; p.edgec = c->edge_collision; p.obs = c->obs; p.obs_mode = c->obs_mode;
-    p.obs_n = c->obs_n; p.obs_elems = obs_elems(snake, c->obs_mode, c->obs_n, c->size); p.N = N; p.S = c->size;
+    // nothing to rebuild and no second observation: the plain step kernel (lighter on registers for large grids)
+    const Kind kind = resets ? K_FUSED : K_STEP;
+    step_outputs(p, c->actions, c->actions_dtype, c->reward, c->done, c->self_collision, c->edge_collision);
     // check_mask: only the resident 9 x 9 step computes it (below); any other kernel leaves "not computed" for every env
     auto no_mask = [&]() -> int {
         if (c->check_mask == nullptr || N == 0) return WURM_OK;
         return hipMemsetAsync(c->check_mask, 0xFF, (size_t)N * 4, (hipStream_t)stream) == hipSuccess ? WURM_OK : WURM_ERR_HIP;
     };
-    p.start_y = c->start_y; p.start_x = c->start_x; p.seed = c->seed; p.call = c->call; p.env_offset = c->env_offset;
+    p.start_y = c->start_y; p.start_x = c->start_x;
     p.inject_food = c->inject_food; p.inject_reset = c->inject_reset; p.done_in = c->pre_done;
     p.obs_after = c->obs_after; p.done_copy = c->done_copy; p.inject_pre_reset = c->inject_pre_reset;
     p.pre_call = c->pre_call; p.post_reset = c->post_reset;
-    if (snake && c->resident != nullptr && N > 0) {
+    const bool mirrored = c->resident != nullptr && N > 0;
+    if (snake && mirrored) {
         p.lds_per_wave = ((p.S * p.S + 15) / 16) * 16;
         if (lane_resident_eligible(p)) {
             // the caller keeps a compact mirror of the state: the step reads that instead of envs (lane_resident.hpp)
@@ -183,7 +254,7 @@ static int fused_entry(bool snake, const wurm_single_call *c, void *stream, int 
                                      (hipStream_t)stream) != hipSuccess)
                 return WURM_ERR_HIP;
             last_route = R_LANE_RESIDENT;
-            if (mirror_state) *mirror_state = 1;
+            mirror = 1;
             return WURM_OK;
         }
         if (lane_wide_resident_eligible(p) && c->resident_lazy) {
@@ -192,7 +263,7 @@ static int fused_entry(bool snake, const wurm_single_call *c, void *stream, int 
             if (launch_lane_wide_resident(p, c->resident, c->resident_valid != 0, c->check_mask, (hipStream_t)stream) != hipSuccess)
                 return WURM_ERR_HIP;
             last_route = R_LANE_WIDE_RESIDENT;
-            if (mirror_state) *mirror_state = 1;
+            mirror = 1;
             return WURM_OK;
         }
         if (no_mask() != WURM_OK) return WURM_ERR_HIP;
@@ -201,60 +272,30 @@ static int fused_entry(bool snake, const wurm_single_call *c, void *stream, int 
             p.resident = c->resident;
             p.resident_valid = c->resident_valid != 0;
             p.resident_lazy = c->resident_lazy != 0;
-            rc = launch<true>(resets ? K_FUSED : K_STEP, p, stream);
-            if (mirror_state) *mirror_state = rc == WURM_OK ? 1 : 0;
+            rc = launch<true>(kind, p, stream);
+            mirror = rc == WURM_OK ? 1 : 0;
             return rc;
         }
         // this call cannot use the mirror: a lazy one is written out to envs before the ordinary kernels read them
-        if (c->resident_lazy && c->resident_valid) {
-            hipError_t err = hipSuccess;
-            if (p.S == 9) err = launch_lane_resident_flush(p, c->resident, (hipStream_t)stream);
-            else if (p.S == 10 || p.S == 11) err = launch_lane_wide_resident_flush(p, c->resident, (hipStream_t)stream);
-            else if (grid_step_eligible(p)) { StepArgs q = p; q.resident = c->resident; err = launch_grid_resident_flush(q, (hipStream_t)stream); }
-            if (err != hipSuccess) return WURM_ERR_HIP;
-        }
+        if (c->resident_lazy && c->resident_valid && write_out_lazy_mirror(true, p, c->resident, stream) == WURM_ERR_HIP)
+            return WURM_ERR_HIP;
     }
-    if (!snake && c->resident != nullptr && N > 0) {
+    if (!snake && mirrored) {
         // SimpleGridworld's mirror (gridworld_lane.hip): one record per env.  resident_valid: 0 = build it in this launch,
         // 1 = current, 2 = refused (the launch that built it found envs outside the lane kernel's domain: the planes stay
         // the state until the caller clears resident_valid again).
         if (no_mask() != WURM_OK) return WURM_ERR_HIP;
-        if (c->resident_valid != 2 && gridworld_lane_step_eligible(p)) {
-            p.resident = c->resident;
-            p.resident_valid = c->resident_valid == 1;
-            p.resident_lazy = c->resident_lazy != 0;
-            if (!p.resident_valid && hipMemsetAsync(c->resident, 0, 16, (hipStream_t)stream) != hipSuccess) return WURM_ERR_HIP;
-            rc = launch<false>(resets ? K_FUSED : K_STEP, p, stream);
-            if (rc != WURM_OK) { if (mirror_state) *mirror_state = 0; return rc; }
-            int state = 1;
-            if (!p.resident_valid) {
-                // the launch built the mirror (and wrote the planes whatever `lazy` says): valid only if it could describe every
-                // env.  One synchronous 4-byte read per BUILD — the first step of an env object, and the step after something
-                // else wrote the state — is what lets every other call be a single launch
-                int odd = 0;
-                if (hipMemcpyAsync(&odd, c->resident, 4, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
-                    hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
-                    return WURM_ERR_HIP;
-                if (odd != 0) state = 2;
-            }
-            if (mirror_state) *mirror_state = state;
-            return WURM_OK;
-        }
+        if (c->resident_valid != 2 && gridworld_lane_step_eligible(p))
+            return launch_gridworld_on_mirror(kind, p, c->resident, c->resident_valid, c->resident_lazy, stream, &mirror);
         // this call cannot use the mirror: a lazy one is written out to envs before the ordinary kernels read them
-        if (c->resident_lazy && c->resident_valid == 1) {
-            StepArgs q = p;
-            q.resident = c->resident;
-            if (launch_gridworld_lane_flush(q, (hipStream_t)stream) != hipSuccess) return WURM_ERR_HIP;
-        }
-        if (mirror_state) *mirror_state = c->resident_valid == 2 ? 2 : 0;
-        const Kind kind_g = resets ? K_FUSED : K_STEP;
-        return launch<false>(kind_g, p, stream);
+        if (c->resident_lazy && c->resident_valid == 1 && write_out_lazy_mirror(false, p, c->resident, stream) != WURM_OK)
+            return WURM_ERR_HIP;
+        mirror = c->resident_valid == 2 ? 2 : 0;
+        return launch<false>(kind, p, stream);
     }
-    if (!(snake && c->resident != nullptr && N > 0) && no_mask() != WURM_OK) return WURM_ERR_HIP;
-    if (mirror_state) *mirror_state = 0;
-    // nothing to rebuild and no second observation: the plain step kernel (lighter on registers for large grids)
-    const Kind kind = resets ? K_FUSED : K_STEP;
-    return snake ? launch<true>(kind, p, stream) : launch<false>(kind, p, stream);
+    if (!mirrored && no_mask() != WURM_OK) return WURM_ERR_HIP;
+    mirror = 0;
+    return launch_kind(snake, kind, p, stream);
 }
 
 int wurm_single_resident_flush(const wurm_single_call *c, void *stream)
@@ -263,13 +304,8 @@ int wurm_single_resident_flush(const wurm_single_call *c, void *stream)
     if (!c->resident || !c->resident_lazy || !c->resident_valid || c->num_envs <= 0) return WURM_OK;
     if (!c->envs) return WURM_ERR_INVALID_ARG;
     StepArgs p = {};
-    p.envs = c->envs; p.N = c->num_envs; p.S = c->size; p.resident = c->resident;
-    hipError_t err;
-    if (c->size == 9) err = launch_lane_resident_flush(p, c->resident, (hipStream_t)stream);
-    else if (c->size == 10 || c->size == 11) err = launch_lane_wide_resident_flush(p, c->resident, (hipStream_t)stream);
-    else if (grid_step_eligible(p)) err = launch_grid_resident_flush(p, (hipStream_t)stream);
-    else return WURM_ERR_INVALID_ARG;
-    return err == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+    p.envs = c->envs; p.N = c->num_envs; p.S = c->size;
+    return write_out_lazy_mirror(true, p, c->resident, stream);
 }
 
 int64_t wurm_single_resident_size(int64_t num_envs, int size, int obs_mode, int obs_n)
@@ -313,8 +349,8 @@ int wurm_grid_resident_flush(const wurm_single_call *c, void *stream)
     if (!c->resident || !c->resident_lazy || c->resident_valid != 1 || c->num_envs <= 0) return WURM_OK;
     if (!c->envs) return WURM_ERR_INVALID_ARG;
     StepArgs p = {};
-    p.envs = c->envs; p.N = c->num_envs; p.S = c->size; p.resident = c->resident;
-    return launch_gridworld_lane_flush(p, (hipStream_t)stream) == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+    p.envs = c->envs; p.N = c->num_envs; p.S = c->size;
+    return write_out_lazy_mirror(false, p, c->resident, stream);
 }
 
 int wurm_single_step_reset(const wurm_single_call *c, void *stream) { return fused_entry(true, c, stream); }
@@ -402,16 +438,8 @@ int wurm_single_check(const float *envs, uint32_t *err, int64_t num_envs, int si
     hipStream_t st = (hipStream_t)stream;
     long long N = num_envs;
     (void)hipGetLastError();
-    switch (cpl) {
-    case 2: WURM_LAUNCH(check_kernel<2>, grid, block, 0, st, envs, err, N, size); break;
-    case 4: WURM_LAUNCH(check_kernel<4>, grid, block, 0, st, envs, err, N, size); break;
-    case 8: WURM_LAUNCH(check_kernel<8>, grid, block, 0, st, envs, err, N, size); break;
-    case 16: WURM_LAUNCH(check_kernel<16>, grid, block, 0, st, envs, err, N, size); break;
-    case 24: WURM_LAUNCH(check_kernel<24>, grid, block, 0, st, envs, err, N, size); break;
-    case 32: WURM_LAUNCH(check_kernel<32>, grid, block, 0, st, envs, err, N, size); break;
-    case 48: WURM_LAUNCH(check_kernel<48>, grid, block, 0, st, envs, err, N, size); break;
-    default: WURM_LAUNCH(check_kernel<64>, grid, block, 0, st, envs, err, N, size); break;
-    }
+    auto go = [&](auto kernel) { WURM_LAUNCH(kernel, grid, block, 0, st, envs, err, N, size); };
+    WURM_CPL_LADDER(cpl, go, check_kernel);
     return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
 }
 
@@ -429,16 +457,8 @@ int wurm_orientations(const float *envs, int64_t *out, int64_t n, int size, void
     long long *o = (long long *)out;
     size_t lds = (size_t)lpw * wpb;
     (void)hipGetLastError();
-    switch (cpl) {
-    case 2: WURM_LAUNCH(orientations_kernel<2>, grid, block, lds, st, envs, o, N, size, lpw); break;
-    case 4: WURM_LAUNCH(orientations_kernel<4>, grid, block, lds, st, envs, o, N, size, lpw); break;
-    case 8: WURM_LAUNCH(orientations_kernel<8>, grid, block, lds, st, envs, o, N, size, lpw); break;
-    case 16: WURM_LAUNCH(orientations_kernel<16>, grid, block, lds, st, envs, o, N, size, lpw); break;
-    case 24: WURM_LAUNCH(orientations_kernel<24>, grid, block, lds, st, envs, o, N, size, lpw); break;
-    case 32: WURM_LAUNCH(orientations_kernel<32>, grid, block, lds, st, envs, o, N, size, lpw); break;
-    case 48: WURM_LAUNCH(orientations_kernel<48>, grid, block, lds, st, envs, o, N, size, lpw); break;
-    default: WURM_LAUNCH(orientations_kernel<64>, grid, block, lds, st, envs, o, N, size, lpw); break;
-    }
+    auto go = [&](auto kernel) { WURM_LAUNCH(kernel, grid, block, lds, st, envs, o, N, size, lpw); };
+    WURM_CPL_LADDER(cpl, go, orientations_kernel);
     return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
 }
 
@@ -448,14 +468,12 @@ int wurm_grid_step(float *envs, const void *actions, int actions_dtype, float *r
                    uint8_t *edge_collision, float *obs, int obs_mode, int obs_n, int64_t num_envs, int size,
                    uint64_t seed, uint64_t call, int64_t env_offset, const int32_t *inject_food, void *stream)
 {
-    int rc = check_common(false, envs, num_envs, size, obs, obs_mode, obs_n, actions_dtype);
+    StepArgs p;
+    int rc = checked_args(false, p, envs, obs, obs_mode, obs_n, num_envs, size, actions_dtype, seed, call, env_offset);
     if (rc) return rc;
     if (num_envs > 0 && (!actions || !reward || !done || !edge_collision)) return WURM_ERR_INVALID_ARG;
-    StepArgs p = {};
-    p.envs = envs; p.actions = const_cast<void *>(actions); p.act_dtype = actions_dtype; p.reward = reward;
-    p.done = done; p.edgec = edge_collision; p.obs = obs; p.obs_mode = obs_mode; p.obs_n = obs_n;
-    p.obs_elems = obs_elems(false, obs_mode, obs_n, size); p.N = num_envs; p.S = size; p.seed = seed; p.call = call;
-    p.env_offset = env_offset; p.inject_food = inject_food;
+    step_outputs(p, actions, actions_dtype, reward, done, nullptr, edge_collision);
+    p.inject_food = inject_food;
     return launch<false>(K_STEP, p, stream);
 }
 
@@ -463,15 +481,13 @@ int wurm_grid_reset(float *envs, const uint8_t *done, float *obs, int obs_mode, 
                     int size, int start_y, int start_x, uint64_t seed, uint64_t call, int64_t env_offset,
                     const int32_t *inject_reset, void *stream)
 {
-    int rc = check_common(false, envs, num_envs, size, obs, obs_mode, obs_n, WURM_ACT_I64);
+    StepArgs p;
+    int rc = checked_args(false, p, envs, obs, obs_mode, obs_n, num_envs, size, WURM_ACT_I64, seed, call, env_offset);
     if (rc) return rc;
-    if (size <= 4) return WURM_ERR_UNSUPPORTED;                                                  // simple_gridworld.py:249-250
-    if (start_y < 0 || start_x < 0 || start_y >= size || start_x >= size) return WURM_ERR_UNSUPPORTED; // :254-260
+    if (size <= 4) return WURM_ERR_UNSUPPORTED; // simple_gridworld.py:249-250
+    if (!start_ok(size, start_y, start_x)) return WURM_ERR_UNSUPPORTED;
     if (num_envs > 0 && !done) return WURM_ERR_INVALID_ARG;
-    StepArgs p = {};
-    p.envs = envs; p.done_in = done; p.obs = obs; p.obs_mode = obs_mode; p.obs_n = obs_n;
-    p.obs_elems = obs_elems(false, obs_mode, obs_n, size); p.N = num_envs; p.S = size; p.start_y = start_y;
-    p.start_x = start_x; p.seed = seed; p.call = call; p.env_offset = env_offset; p.inject_reset = inject_reset;
+    p.done_in = done; p.start_y = start_y; p.start_x = start_x; p.inject_reset = inject_reset;
     return launch<false>(K_RESET, p, stream);
 }
 
@@ -479,12 +495,9 @@ int wurm_grid_observe(const float *envs, float *obs, int obs_mode, int obs_n, in
                       void *stream)
 {
     if (obs_mode == WURM_OBS_NONE) return WURM_ERR_INVALID_ARG;
-    int rc = check_common(false, envs, num_envs, size, obs, obs_mode, obs_n, WURM_ACT_I64);
-    if (rc) return rc;
-    StepArgs p = {};
-    p.envs = const_cast<float *>(envs); p.obs = obs; p.obs_mode = obs_mode; p.obs_n = obs_n;
-    p.obs_elems = obs_elems(false, obs_mode, obs_n, size); p.N = num_envs; p.S = size;
-    return launch<false>(K_OBSERVE, p, stream);
+    StepArgs p;
+    int rc = checked_args(false, p, const_cast<float *>(envs), obs, obs_mode, obs_n, num_envs, size, WURM_ACT_I64, 0, 0, 0);
+    return rc ? rc : launch<false>(K_OBSERVE, p, stream);
 }
 
 int wurm_grid_rollout(float *envs, const void *actions, int actions_dtype, float *reward, uint8_t *done,
@@ -492,18 +505,10 @@ int wurm_grid_rollout(float *envs, const void *actions, int actions_dtype, float
                       int64_t num_steps, int start_y, int start_x, uint64_t seed, uint64_t call0,
                       int64_t env_offset, const int32_t *inject_food, const int32_t *inject_reset, void *stream)
 {
-    int rc = check_common(false, envs, num_envs, size, obs, obs_mode, obs_n, actions_dtype);
-    if (rc) return rc;
-    if (num_steps < 0) return WURM_ERR_INVALID_ARG;
-    if (size <= 4) return WURM_ERR_UNSUPPORTED;
-    if (start_y < 0 || start_x < 0 || start_y >= size || start_x >= size) return WURM_ERR_UNSUPPORTED;
-    if (num_envs > 0 && num_steps > 0 && (!actions || !reward || !done || !edge_collision)) return WURM_ERR_INVALID_ARG;
-    if (num_steps == 0) return WURM_OK;
-    StepArgs p = {};
-    p.envs = envs; p.actions = const_cast<void *>(actions); p.act_dtype = actions_dtype; p.reward = reward;
-    p.done = done; p.edgec = edge_collision; p.obs = obs; p.obs_mode = obs_mode; p.obs_n = obs_n;
-    p.obs_elems = obs_elems(false, obs_mode, obs_n, size); p.N = num_envs; p.S = size; p.T = num_steps;
-    p.start_y = start_y; p.start_x = start_x; p.seed = seed; p.call = call0; p.env_offset = env_offset;
+    StepArgs p;
+    int rc = rollout_args(false, p, envs, actions, actions_dtype, reward, done, nullptr, edge_collision, obs, obs_mode, obs_n,
+                          num_envs, size, num_steps, start_y, start_x, seed, call0, env_offset);
+    if (rc || num_steps == 0) return rc;
     p.inject_food = inject_food; p.inject_reset = inject_reset;
     return launch<false>(K_ROLLOUT, p, stream);
 }
@@ -522,18 +527,10 @@ int wurm_single_rollout_resident(float *envs, void *actions, int actions_dtype, 
     if (!resident || !resident_valid)
         return wurm_single_rollout(envs, actions, actions_dtype, reward, done, self_collision, edge_collision, obs, obs_mode, obs_n,
                                    num_envs, size, num_steps, seed, call0, env_offset, nullptr, nullptr, stream);
-    int rc = check_common(true, envs, num_envs, size, obs, obs_mode, obs_n, actions_dtype);
-    if (rc) return rc;
-    if (num_steps < 0) return WURM_ERR_INVALID_ARG;
-    if (size <= 8) return WURM_ERR_UNSUPPORTED;
-    if (num_envs > 0 && num_steps > 0 && (!actions || !reward || !done || !self_collision || !edge_collision))
-        return WURM_ERR_INVALID_ARG;
-    if (num_steps == 0 || num_envs == 0) return WURM_OK;
-    StepArgs p = {};
-    p.envs = envs; p.actions = actions; p.act_dtype = actions_dtype; p.reward = reward; p.done = done;
-    p.selfc = self_collision; p.edgec = edge_collision; p.obs = obs; p.obs_mode = obs_mode; p.obs_n = obs_n;
-    p.obs_elems = obs_elems(true, obs_mode, obs_n, size); p.N = num_envs; p.S = size; p.T = num_steps; p.seed = seed;
-    p.call = call0; p.env_offset = env_offset;
+    StepArgs p;
+    int rc = rollout_args(true, p, envs, actions, actions_dtype, reward, done, self_collision, edge_collision, obs, obs_mode,
+                          obs_n, num_envs, size, num_steps, 0, 0, seed, call0, env_offset);
+    if (rc || num_steps == 0 || num_envs == 0) return rc;
     if (grid_rollout_eligible(p) && grid_resident_eligible(p)) {
         p.resident = resident;
         p.resident_valid = *resident_valid != 0;
@@ -542,13 +539,7 @@ int wurm_single_rollout_resident(float *envs, void *actions, int actions_dtype, 
         *resident_valid = rc == WURM_OK ? 1 : 0;
         return rc;
     }
-    if (resident_lazy && *resident_valid) {
-        hipError_t err = hipSuccess;
-        if (size == 9) err = launch_lane_resident_flush(p, resident, (hipStream_t)stream);
-        else if (size == 10 || size == 11) err = launch_lane_wide_resident_flush(p, resident, (hipStream_t)stream);
-        else if (grid_step_eligible(p)) { StepArgs q = p; q.resident = resident; err = launch_grid_resident_flush(q, (hipStream_t)stream); }
-        if (err != hipSuccess) return WURM_ERR_HIP;
-    }
+    if (resident_lazy && *resident_valid && write_out_lazy_mirror(true, p, resident, stream) == WURM_ERR_HIP) return WURM_ERR_HIP;
     *resident_valid = 0;
     return launch<true>(K_ROLLOUT, p, stream);
 }
@@ -568,39 +559,13 @@ int wurm_grid_rollout_resident(float *envs, const void *actions, int actions_dty
     if (!resident || !resident_valid)
         return wurm_grid_rollout(envs, actions, actions_dtype, reward, done, edge_collision, obs, obs_mode, obs_n, num_envs, size,
                                  num_steps, start_y, start_x, seed, call0, env_offset, nullptr, nullptr, stream);
-    int rc = check_common(false, envs, num_envs, size, obs, obs_mode, obs_n, actions_dtype);
-    if (rc) return rc;
-    if (num_steps < 0) return WURM_ERR_INVALID_ARG;
-    if (size <= 4) return WURM_ERR_UNSUPPORTED;
-    if (start_y < 0 || start_x < 0 || start_y >= size || start_x >= size) return WURM_ERR_UNSUPPORTED;
-    if (num_envs > 0 && num_steps > 0 && (!actions || !reward || !done || !edge_collision)) return WURM_ERR_INVALID_ARG;
-    if (num_steps == 0 || num_envs == 0) return WURM_OK;
-    StepArgs p = {};
-    p.envs = envs; p.actions = const_cast<void *>(actions); p.act_dtype = actions_dtype; p.reward = reward;
-    p.done = done; p.edgec = edge_collision; p.obs = obs; p.obs_mode = obs_mode; p.obs_n = obs_n;
-    p.obs_elems = obs_elems(false, obs_mode, obs_n, size); p.N = num_envs; p.S = size; p.T = num_steps;
-    p.start_y = start_y; p.start_x = start_x; p.seed = seed; p.call = call0; p.env_offset = env_offset;
-    if (*resident_valid != 2 && gridworld_lane_eligible(p)) {
-        p.resident = resident;
-        p.resident_valid = *resident_valid == 1;
-        p.resident_lazy = resident_lazy != 0;
-        if (!p.resident_valid && hipMemsetAsync(resident, 0, 16, (hipStream_t)stream) != hipSuccess) return WURM_ERR_HIP;
-        rc = launch<false>(K_ROLLOUT, p, stream);
-        if (rc != WURM_OK) { *resident_valid = 0; return rc; }
-        if (!p.resident_valid) { // the launch built the mirror: valid only if it could describe every env (see fused_entry)
-            int odd = 0;
-            if (hipMemcpyAsync(&odd, resident, 4, hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
-                hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
-                return WURM_ERR_HIP;
-            *resident_valid = odd != 0 ? 2 : 1;
-        }
-        return WURM_OK;
-    }
-    if (resident_lazy && *resident_valid == 1) {
-        StepArgs q = p;
-        q.resident = resident;
-        if (launch_gridworld_lane_flush(q, (hipStream_t)stream) != hipSuccess) return WURM_ERR_HIP;
-    }
+    StepArgs p;
+    int rc = rollout_args(false, p, envs, actions, actions_dtype, reward, done, nullptr, edge_collision, obs, obs_mode, obs_n,
+                          num_envs, size, num_steps, start_y, start_x, seed, call0, env_offset);
+    if (rc || num_steps == 0 || num_envs == 0) return rc;
+    if (*resident_valid != 2 && gridworld_lane_eligible(p)) // (a launch that builds the mirror reads its verdict: see fused_entry)
+        return launch_gridworld_on_mirror(K_ROLLOUT, p, resident, *resident_valid, resident_lazy, stream, resident_valid);
+    if (resident_lazy && *resident_valid == 1 && write_out_lazy_mirror(false, p, resident, stream) != WURM_OK) return WURM_ERR_HIP;
     if (*resident_valid != 2) *resident_valid = 0;
     return launch<false>(K_ROLLOUT, p, stream);
 }

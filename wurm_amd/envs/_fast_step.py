@@ -27,9 +27,16 @@ time per call, not by the GPU, so:
     then on every step writes it), any other entry point goes through `_touch()`, a tensor the caller holds is watched for
     in-place edits through its version counter (DESIGN.md §5, §7 deviation 9).
 
-The host class provides: num_envs, size, device, seed, env_offset, observation_mode, lazy_reset, _CHANNELS,
-_STEP_SLOT (entry point name), _mode_info(mode) -> (mode code, n, obs shape), _lazy_supported(), _launch_reset(envs,
-done, obs, mode code, n, call), _configure_call(block), _make_out(i) -> what step returns for slot i.
+`reset`, `rollout`, `_get_rgb` and the common part of `policy_rollout` are the mixin's as well: the two classes differ there in
+names and in SimpleGridworld's start location only.
+
+The host class provides: num_envs, size, device, seed, env_offset, observation_mode, lazy_reset, _mode_cache, _CHANNELS,
+_NAME, _STEP_SLOT / _ROLLOUT_FNS (plain, with a mirror) / _POLICY_FN (entry point names), _FLAG_KEYS (result keys of the flag
+rows an entry point writes), _BAD_STATUS, _parse_mode(mode) -> (mode code, n), _obs_shape(mode), _observe(mode),
+_lazy_supported(), _cannot_reset() -> the exception a reset that has to create an env raises (None: it can; what no reset at all
+can do, SingleSnake's other snake lengths, it raises itself), _start_args()
+-> the start location the resetting entry points take, or (), _launch_reset(envs, done, obs, mode code, n, call),
+_configure_call(block), _make_out(i) -> what step returns for slot i.
 """
 import ctypes
 import os
@@ -243,6 +250,8 @@ def _make_stepper(name, blk_addr, slabs_addr):
 class FastStepMixin(object):
     # the library's mirror entry points of the class: size with / without the batch-size threshold, flush
     _RESIDENT_FNS = ('wurm_single_resident_bytes', 'wurm_single_resident_size', 'wurm_single_resident_flush')
+    # rollout() of no steps: True = the mirror is not looked at (SingleSnake), False = it is brought in line with the mode first
+    _EMPTY_ROLLOUT_SKIPS_MIRROR = False
 
     def _fast_init(self):
         N = self.num_envs
@@ -663,3 +672,151 @@ class FastStepMixin(object):
         if obs is NotImplemented:
             return False, None
         return True, obs
+
+    def reset(self, done: torch.Tensor = None, return_observations: bool = True):
+        """Resets environments that have finished (reference single_snake.py:322-342, simple_gridworld.py:225-245).
+
+        Args:
+            done: A 1D Tensor of length self.num_envs (any dtype; (N,1) is accepted). A non-zero value means the
+                corresponding environment needs to be reset.  None: use the `done` of the last step.
+            return_observations: extension — pass False to skip the observation the reference's callers discard
+                (experiments/main.py:227).
+
+        Called with the very `done` the last `step` returned (and nothing in between), the reset is postponed into the
+        next step's launch (module docstring); the observation it returns then comes from the step's launch as well.
+        """
+        if done is None:
+            done = self.done
+        handled, obs = self._try_lazy_reset(done, return_observations)
+        if handled:
+            return obs
+        done = done.view((done.shape[0]))
+        if done.dtype != torch.bool:
+            done = done != 0
+        if done.device != self.device:
+            done = done.to(self.device)
+        return self._reset(done.contiguous(), observe=return_observations)
+
+    def _reset(self, done: torch.Tensor, observe: bool = True):
+        err = self._cannot_reset()
+        if err is not None:
+            # the reference raises only when an env actually has to be created
+            if bool(done.any()):
+                raise err
+            return self._observe(self.observation_mode) if observe else None
+        envs = self._state()
+        m, n, obs = self._out_obs(observe)
+        self._launch_reset(envs, done, obs, m, n, self._next_call())
+        return obs
+
+    # ------------------------------------------------------------------ observations, fused loops
+
+    def _mode_info(self, observation_mode: str):
+        """(mode code, window size, observation shape) of an observation mode string, cached per string."""
+        key = (observation_mode, self.observation_mode if isinstance(observation_mode, str) and
+               observation_mode.startswith('partial_') else None)
+        info = self._mode_cache.get(key)
+        if info is None:
+            m, n = self._parse_mode(observation_mode)
+            shape = self._obs_shape(observation_mode if m != _lib.OBS_PARTIAL else f'partial_{n}')
+            info = self._mode_cache[key] = (m, n, shape)
+        return info
+
+    def _out_mode(self):
+        """`_mode_info` of the env's own mode, as reset and rollout ask for it"""
+        return self._mode_info(self.observation_mode)
+
+    def _out_obs(self, want: bool, lead: tuple = ()):
+        """(mode code, window size, a fresh observation tensor with `lead` in front of its shape), or "no observation" """
+        if not want:
+            return _lib.OBS_NONE, 0, None
+        m, n, shape = self._out_mode()
+        return m, n, torch.empty(lead + tuple(shape), dtype=torch.float32, device=self.device)
+
+    def _get_rgb(self) -> torch.Tensor:
+        """reference single_snake.py:104-128, simple_gridworld.py:88-109 — int16 RGB image (N,3,S,S)"""
+        return (self._observe('default') * 255).round().short()
+
+    def rollout(self, actions: torch.Tensor, return_observations: bool = True) -> dict:
+        """T iterations of `obs, r, d, info = env.step(actions[t]); env.reset(d)` in one kernel launch.
+
+        actions: (T, num_envs) int64/int32 on the device (SingleSnake sanitises them in place).  Returns a dict of
+        (T, N, ...) tensors (`observations`, `rewards`, `dones` and the class's collision flags), bit-identical to the
+        Python loop.
+        """
+        if actions.dtype not in (torch.int, torch.long):
+            raise TypeError('actions Tensor must be an integer type i.e. {torch.IntTensor, torch.LongTensor}')
+        if actions.dim() != 2 or actions.shape[1] != self.num_envs:
+            raise RuntimeError('Must have the same number of actions as environments.')
+        if not actions.is_contiguous() or actions.device != self.device:
+            raise RuntimeError('rollout actions must be a contiguous device tensor')
+        start = self._start_args()
+        T, N = actions.shape
+        m, n, obs = self._out_obs(return_observations, (T,))
+        reward = torch.empty((T, N), dtype=torch.float32, device=self.device)
+        flags = torch.empty((len(self._FLAG_KEYS), T, N), dtype=torch.bool, device=self.device).unbind(0)
+        dt = _lib.ACT_I64 if actions.dtype == torch.long else _lib.ACT_I32
+        # With a mirror (large batches) the launch reads it instead of the planes where its kernels serve the rollout and
+        # keeps it current, lazy: without writing the planes (wurm_single_rollout_resident, wurm_grid_rollout_resident);
+        # where they do not, the library writes a lazy mirror out, rolls out on the planes and reports the mirror stale.
+        # Same protocol as step(): a postponed reset is applied first, a watched tensor is checked for in-place edits,
+        # nothing is "touched".
+        mirrored = False
+        if T > 0 or not self._EMPTY_ROLLOUT_SKIPS_MIRROR:
+            if self._fs.pending:
+                self._flush()
+            self._mirror_sync()
+            self._setup_mirror(*((m, n) if return_observations else self._out_mode()[:2]))
+            mirrored = T > 0 and bool(self._c.resident)
+        c = self._c
+        if mirrored:
+            envs = self._checked(self._envs)
+            self._fs.last_fresh = False
+            self._chk_void_at = self._fs.steps
+            valid = ctypes.c_int(c.resident_valid)
+            mirror = (c.resident, ctypes.addressof(valid), int(c.resident_lazy))
+        else:
+            envs = self._state()
+            mirror = (None, None)   # (the plain entry point: no recorded outcomes to inject)
+        rc = _lib.call(self.device.index, getattr(_lib.lib(), self._ROLLOUT_FNS[mirrored]),
+                       _lib.ptr(envs), _lib.ptr(actions), dt, _lib.ptr(reward), *[_lib.ptr(f) for f in flags], _lib.ptr(obs),
+                       m, n, _lib.i64(N), self.size, _lib.i64(T), *start, _lib.u64(self.seed),
+                       _lib.u64(self._next_call(2 * T)), _lib.i64(self.env_offset), *mirror,
+                       _lib.stream_ptr(self.device.index))
+        if mirrored:
+            c.resident_valid = valid.value if rc == _lib.OK else 0
+        _lib.check(rc, self._NAME + '.rollout')
+        self._done_all_false()  # every done env was reset
+        return dict(observations=obs, rewards=reward, **dict(zip(self._FLAG_KEYS, flags)))
+
+    def _policy_rollout(self, params: torch.Tensor, state: torch.Tensor, num_steps: int, check: bool, mode_args: tuple) -> dict:
+        """What the classes' policy_rollout share once their preconditions hold (mode_args: what the class's entry point
+        takes between `status` and the batch size)."""
+        shape = self._mode_info(self.observation_mode)[2]
+        N, T, E = self.num_envs, int(num_steps), int(torch.Size(shape[1:]).numel())
+        if params.dtype != torch.float32 or params.device != self.device or not params.is_contiguous() or \
+                params.numel() != 64 * E + 64 + 64 * 64 + 64 + 4 * 64 + 4 + 64 + 1:
+            raise RuntimeError('params must be the contiguous fp32 device tensor of pack_policy_params for this observation size')
+        if state.device != self.device or state.numel() != N * E:
+            raise RuntimeError('state must be the current observation of every env on the env device')
+        state = state.to(torch.float32).contiguous()
+        envs = self._state()
+        dev = self.device
+        actions = torch.empty((T, N), dtype=torch.long, device=dev)
+        probs = torch.empty((T, N, 4), dtype=torch.float32, device=dev)
+        values = torch.empty((T, N), dtype=torch.float32, device=dev)
+        reward = torch.empty((T, N), dtype=torch.float32, device=dev)
+        flags = torch.empty((len(self._FLAG_KEYS), T, N), dtype=torch.bool, device=dev).unbind(0)
+        obs = torch.empty((T,) + tuple(shape), dtype=torch.float32, device=dev)
+        status = torch.empty(N, dtype=torch.uint8, device=dev)
+        rc = _lib.call(dev.index, getattr(_lib.lib(), self._POLICY_FN),
+                       _lib.ptr(envs), _lib.ptr(state), _lib.ptr(params), _lib.ptr(actions), _lib.ptr(probs),
+                       _lib.ptr(values), _lib.ptr(reward), *[_lib.ptr(f) for f in flags], _lib.ptr(obs), _lib.ptr(status),
+                       *mode_args, _lib.i64(N), self.size, _lib.i64(T), *self._start_args(), _lib.u64(self.seed),
+                       _lib.u64(self._next_call(2 * T)), _lib.i64(self.env_offset), _lib.stream_ptr(dev.index))
+        _lib.check(rc, self._NAME + '.policy_rollout')
+        if check and T > 0 and bool(status.any()):
+            raise RuntimeError(f'policy_rollout: {self._BAD_STATUS} (status != 0); they were left untouched')
+        self._done_all_false()  # every done env was reset
+        return dict(actions=actions, probs=probs, values=values, rewards=reward, **dict(zip(self._FLAG_KEYS, flags)),
+                    observations=obs, state=obs[-1] if T > 0 else state.reshape(shape), status=status)

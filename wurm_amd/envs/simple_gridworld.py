@@ -5,8 +5,6 @@ iteration, see wurm_amd/envs/_fast_step.py."""
 from collections import namedtuple
 from typing import Tuple
 
-import ctypes
-
 import torch
 
 from wurm_amd import _lib
@@ -22,7 +20,12 @@ class SimpleGridworld(FastStepMixin):
     respawns), moving on to the border ring ends the episode (reference simple_gridworld.py:16-42)."""
 
     _CHANNELS = 2
+    _NAME = 'SimpleGridworld'
     _STEP_SLOT = 'wurm_grid_step_slot'
+    _ROLLOUT_FNS = ('wurm_grid_rollout', 'wurm_grid_rollout_resident')
+    _POLICY_FN = 'wurm_grid_policy_rollout'
+    _FLAG_KEYS = ('dones', 'edge_collision')
+    _BAD_STATUS = 'some envs do not hold exactly one agent and one food'
     _RESIDENT_FNS = ('wurm_grid_resident_bytes', 'wurm_grid_resident_size', 'wurm_grid_resident_flush')
 
     spec = Spec(float('inf'))
@@ -93,6 +96,17 @@ class SimpleGridworld(FastStepMixin):
         sy, sx = self.start_location if self.start_location is not None else (-1, -1)
         c.start_y, c.start_x = int(sy), int(sx)
 
+    def _start_args(self):
+        if self.start_location is None:
+            raise NotImplementedError("Haven't implemented random starting locations")
+        return int(self.start_location[0]), int(self.start_location[1])
+
+    def _cannot_reset(self):
+        if self.size <= 4:  # reference :249-260
+            return NotImplementedError('Environemnts smaller than this don\'t make sense.')
+        if self.start_location is None:
+            return NotImplementedError("Haven't implemented random starting locations")
+
     def _launch_reset(self, envs, done, obs, m, n, call):
         rc = _lib.call(self.device.index, _lib.lib().wurm_grid_reset, _lib.ptr(envs), _lib.ptr(done), _lib.ptr(obs), m, n,
                        _lib.i64(self.num_envs), self.size, int(self.start_location[0]), int(self.start_location[1]),
@@ -100,13 +114,14 @@ class SimpleGridworld(FastStepMixin):
                        _lib.stream_ptr(self.device.index))
         _lib.check(rc, 'SimpleGridworld.reset')
 
-    def _mode_info(self, observation_mode: str):
-        info = self._mode_cache.get(observation_mode)
-        if info is None:
-            shape = self._obs_shape(observation_mode)
-            m, n = _lib.parse_obs_mode(observation_mode)
-            info = self._mode_cache[observation_mode] = (m, n, shape)
-        return info
+    def _parse_mode(self, observation_mode: str):
+        self._obs_shape(observation_mode)  # (what is no mode of this class raises here: reference :132-133)
+        return _lib.parse_obs_mode(observation_mode)
+
+    def _out_mode(self):
+        # (reset and rollout parse the string first: one that is no mode of any class is a ValueError there)
+        m, n = _lib.parse_obs_mode(self.observation_mode)
+        return m, n, self._obs_shape(self.observation_mode)
 
     def _obs_shape(self, mode: str):
         N, S = self.num_envs, self.size
@@ -128,10 +143,6 @@ class SimpleGridworld(FastStepMixin):
         _lib.check(rc, 'SimpleGridworld._observe')
         return obs
 
-    def _get_rgb(self) -> torch.Tensor:
-        """reference :88-109"""
-        return (self._observe('default') * 255).round().short()
-
     def step(self, actions: torch.Tensor) -> (torch.Tensor, torch.Tensor, torch.Tensor, dict):
         """reference :135-202 (actions are not modified).  One launch; a reset(done) postponed by the previous iteration
         (wurm_amd/envs/_fast_step.py) is applied in front of the transition."""
@@ -139,86 +150,6 @@ class SimpleGridworld(FastStepMixin):
 
     def _make_out(self, i: int):
         return self._v_obs[i], self._v_reward[i], self._v_done2[i], {'edge_collision': self._v_edgec[i]}
-
-    def _reset(self, done: torch.Tensor, observe: bool = True):
-        if self.size <= 4 or self.start_location is None:
-            # reference :249-260 raises only when an env actually has to be created
-            if bool(done.any()):
-                if self.size <= 4:
-                    raise NotImplementedError('Environemnts smaller than this don\'t make sense.')
-                raise NotImplementedError("Haven't implemented random starting locations")
-            return self._observe(self.observation_mode) if observe else None
-        envs = self._state()
-        if observe:
-            m, n = _lib.parse_obs_mode(self.observation_mode)
-            obs = torch.empty(self._obs_shape(self.observation_mode), dtype=torch.float32, device=self.device)
-        else:
-            m, n, obs = _lib.OBS_NONE, 0, None
-        self._launch_reset(envs, done, obs, m, n, self._next_call())
-        return obs
-
-    def reset(self, done: torch.Tensor = None, return_observations: bool = True):
-        """reference :225-245"""
-        if done is None:
-            done = self.done
-        handled, obs = self._try_lazy_reset(done, return_observations)
-        if handled:
-            return obs
-        done = done.view((done.shape[0]))
-        if done.dtype != torch.bool:
-            done = done != 0
-        if done.device != self.device:
-            done = done.to(self.device)
-        return self._reset(done.contiguous(), observe=return_observations)
-
-    def rollout(self, actions: torch.Tensor, return_observations: bool = True) -> dict:
-        """T iterations of `step(actions[t]); reset(done)` in one launch (see SingleSnake.rollout)."""
-        if actions.dtype not in (torch.int, torch.long):
-            raise TypeError('actions Tensor must be an integer type i.e. {torch.IntTensor, torch.LongTensor}')
-        if actions.dim() != 2 or actions.shape[1] != self.num_envs:
-            raise RuntimeError('Must have the same number of actions as environments.')
-        if not actions.is_contiguous() or actions.device != self.device:
-            raise RuntimeError('rollout actions must be a contiguous device tensor')
-        if self.start_location is None:
-            raise NotImplementedError("Haven't implemented random starting locations")
-        T, N = actions.shape
-        if return_observations:
-            m, n = _lib.parse_obs_mode(self.observation_mode)
-            obs = torch.empty((T,) + self._obs_shape(self.observation_mode), dtype=torch.float32, device=self.device)
-        else:
-            m, n, obs = _lib.OBS_NONE, 0, None
-        reward = torch.empty((T, N), dtype=torch.float32, device=self.device)
-        flags = torch.empty((2, T, N), dtype=torch.bool, device=self.device)
-        dt = _lib.ACT_I64 if actions.dtype == torch.long else _lib.ACT_I32
-        # The mirror (round 6; large batches: wurm_grid_resident_bytes): the launch reads the records instead of scanning the
-        # planes when they describe the state, keeps them current, and — lazy — does not write the planes; no flag pass
-        # behind it (wurm_grid_rollout_resident).  Same protocol as step(): a postponed reset is applied first, a watched
-        # tensor is checked for in-place edits, nothing is "touched".
-        if self._fs.pending:
-            self._flush()
-        self._mirror_sync()
-        self._setup_mirror(*_lib.parse_obs_mode(self.observation_mode))
-        c = self._c
-        if c.resident and T > 0:
-            envs = self._checked(self._envs)
-            self._fs.last_fresh = False
-            valid = ctypes.c_int(c.resident_valid)
-            rc = _lib.call(self.device.index, _lib.lib().wurm_grid_rollout_resident,
-                _lib.ptr(envs), _lib.ptr(actions), dt, _lib.ptr(reward), _lib.ptr(flags[0]), _lib.ptr(flags[1]), _lib.ptr(obs),
-                m, n, _lib.i64(N), self.size, _lib.i64(T), int(self.start_location[0]), int(self.start_location[1]),
-                _lib.u64(self.seed), _lib.u64(self._next_call(2 * T)), _lib.i64(self.env_offset), c.resident,
-                ctypes.addressof(valid), int(c.resident_lazy), _lib.stream_ptr(self.device.index))
-            c.resident_valid = valid.value if rc == _lib.OK else 0
-        else:
-            envs = self._state()
-            rc = _lib.call(self.device.index, _lib.lib().wurm_grid_rollout,
-                _lib.ptr(envs), _lib.ptr(actions), dt,
-                _lib.ptr(reward), _lib.ptr(flags[0]), _lib.ptr(flags[1]), _lib.ptr(obs), m, n, _lib.i64(N), self.size,
-                _lib.i64(T), int(self.start_location[0]), int(self.start_location[1]), _lib.u64(self.seed),
-                _lib.u64(self._next_call(2 * T)), _lib.i64(self.env_offset), None, None, _lib.stream_ptr(self.device.index))
-        _lib.check(rc, 'SimpleGridworld.rollout')
-        self._done_all_false()
-        return {'observations': obs, 'rewards': reward, 'dones': flags[0], 'edge_collision': flags[1]}
 
     def policy_rollout(self, params: torch.Tensor, state: torch.Tensor, num_steps: int, check: bool = True) -> dict:
         """T iterations of `probs, value = model(state); action = Categorical(probs).sample(); state, reward, done, info =
@@ -234,36 +165,7 @@ class SimpleGridworld(FastStepMixin):
             raise NotImplementedError("Haven't implemented random starting locations")
         if self.size <= 4 or self.size > 64:
             raise NotImplementedError(f'policy_rollout: grid size {self.size}; the fused actor serves sizes 5 to 64')
-        N, T, E = self.num_envs, int(num_steps), 4
-        if params.dtype != torch.float32 or params.device != self.device or not params.is_contiguous() or \
-                params.numel() != 64 * E + 64 + 64 * 64 + 64 + 4 * 64 + 4 + 64 + 1:
-            raise RuntimeError('params must be the contiguous fp32 device tensor of pack_policy_params for this observation size')
-        if state.device != self.device or state.numel() != N * E:
-            raise RuntimeError('state must be the current observation of every env on the env device')
-        state = state.to(torch.float32).contiguous()
-        envs = self._state()
-        dev = self.device
-        actions = torch.empty((T, N), dtype=torch.long, device=dev)
-        probs = torch.empty((T, N, 4), dtype=torch.float32, device=dev)
-        values = torch.empty((T, N), dtype=torch.float32, device=dev)
-        reward = torch.empty((T, N), dtype=torch.float32, device=dev)
-        flags = torch.empty((2, T, N), dtype=torch.bool, device=dev)
-        obs = torch.empty((T, N, E), dtype=torch.float32, device=dev)
-        status = torch.empty(N, dtype=torch.uint8, device=dev)
-        rc = _lib.call(dev.index, _lib.lib().wurm_grid_policy_rollout,
-                       _lib.ptr(envs), _lib.ptr(state), _lib.ptr(params), _lib.ptr(actions), _lib.ptr(probs),
-                       _lib.ptr(values), _lib.ptr(reward), _lib.ptr(flags[0]), _lib.ptr(flags[1]), _lib.ptr(obs),
-                       _lib.ptr(status), _lib.i64(N), self.size, _lib.i64(T), int(self.start_location[0]),
-                       int(self.start_location[1]), _lib.u64(self.seed), _lib.u64(self._next_call(2 * T)),
-                       _lib.i64(self.env_offset), _lib.stream_ptr(dev.index))
-        _lib.check(rc, 'SimpleGridworld.policy_rollout')
-        if check and T > 0 and bool(status.any()):
-            raise RuntimeError('policy_rollout: some envs do not hold exactly one agent and one food (status != 0); '
-                               'they were left untouched')
-        self._done_all_false()  # every done env was reset
-        return {'actions': actions, 'probs': probs, 'values': values, 'rewards': reward, 'dones': flags[0],
-                'edge_collision': flags[1], 'observations': obs, 'state': obs[-1] if T > 0 else state.reshape(N, E),
-                'status': status}
+        return self._policy_rollout(params, state, num_steps, check, ())
 
     def _consistent(self):
         pass

@@ -14,8 +14,6 @@ Per-call path: one launch per `step(a); reset(done)` iteration, see wurm_amd/env
 """
 from collections import namedtuple
 
-import ctypes
-
 import torch
 
 from wurm_amd import _lib
@@ -37,7 +35,13 @@ class SingleSnake(FastStepMixin):
     (reference single_snake.py:22-47)."""
 
     _CHANNELS = 3
+    _NAME = 'SingleSnake'
     _STEP_SLOT = 'wurm_single_step_slot'
+    _ROLLOUT_FNS = ('wurm_single_rollout', 'wurm_single_rollout_resident')
+    _POLICY_FN = 'wurm_single_policy_rollout_mode'
+    _FLAG_KEYS = ('dones', 'self_collision', 'edge_collision')
+    _BAD_STATUS = 'some envs are not well-formed snakes'
+    _EMPTY_ROLLOUT_SKIPS_MIRROR = True   # rollout(): no steps, no look at the mirror (9 x 9's is not the rollout's anyway)
 
     spec = Spec(float('inf'))
     metadata = {
@@ -105,6 +109,17 @@ class SingleSnake(FastStepMixin):
     def _configure_call(self, c):
         pass
 
+    def _start_args(self):
+        return ()
+
+    def _cannot_reset(self):
+        # (a snake length this build does not make is refused at once, whether or not an env has to be created — the size
+        # only when one has to be, reference :346-347: that one is handed back for `_reset` to raise)
+        if self.initial_snake_length != 3:
+            raise NotImplementedError('Only initial snake length = 3 has been implemented.')
+        if self.size <= 8:  # reference :346-347
+            return NotImplementedError('Cannot make an env this small without making this code more clever')
+
     def _launch_reset(self, envs, done, obs, m, n, call):
         rc = _lib.call(self.device.index, _lib.lib().wurm_single_reset, _lib.ptr(envs), _lib.ptr(done), _lib.ptr(obs),
                        m, n, _lib.i64(self.num_envs), self.size, _lib.u64(self.seed), _lib.u64(call),
@@ -133,17 +148,6 @@ class SingleSnake(FastStepMixin):
             return _lib.OBS_PARTIAL, int(src.split('_')[-1])
         raise Exception  # reference :194-195
 
-    def _mode_info(self, observation_mode: str):
-        """(mode code, window size, observation shape) of an observation mode string, cached per string."""
-        key = (observation_mode, self.observation_mode if isinstance(observation_mode, str) and
-               observation_mode.startswith('partial_') else None)
-        info = self._mode_cache.get(key)
-        if info is None:
-            m, n = self._parse_mode(observation_mode)
-            shape = self._obs_shape(observation_mode if m != _lib.OBS_PARTIAL else f'partial_{n}')
-            info = self._mode_cache[key] = (m, n, shape)
-        return info
-
     # ------------------------------------------------------------------ observations
 
     def _observe(self, observation_mode: str = 'default') -> torch.Tensor:
@@ -155,10 +159,6 @@ class SingleSnake(FastStepMixin):
                                             self.size, _lib.stream_ptr(self.device.index))
         _lib.check(rc, 'SingleSnake._observe')
         return obs
-
-    def _get_rgb(self) -> torch.Tensor:
-        """reference :104-128 — int16 RGB image (N,3,S,S)"""
-        return (self._observe('default') * 255).round().short()
 
     # ------------------------------------------------------------------ step
 
@@ -175,47 +175,6 @@ class SingleSnake(FastStepMixin):
 
     # ------------------------------------------------------------------ reset
 
-    def _reset(self, done: torch.Tensor, observe: bool = True):
-        if self.initial_snake_length != 3:
-            raise NotImplementedError('Only initial snake length = 3 has been implemented.')
-        if self.size <= 8:
-            # reference :346-347 raises only when an env actually has to be created
-            if bool(done.any()):
-                raise NotImplementedError('Cannot make an env this small without making this code more clever')
-            return self._observe(self.observation_mode) if observe else None
-        envs = self._state()
-        if observe:
-            m, n, shape = self._mode_info(self.observation_mode)
-            obs = torch.empty(shape, dtype=torch.float32, device=self.device)
-        else:
-            m, n, obs = _lib.OBS_NONE, 0, None
-        self._launch_reset(envs, done, obs, m, n, self._next_call())
-        return obs
-
-    def reset(self, done: torch.Tensor = None, return_observations: bool = True):
-        """Resets environments in which the snake has died (reference :322-342).
-
-        Args:
-            done: A 1D Tensor of length self.num_envs (any dtype; (N,1) is accepted). A non-zero value means the
-                corresponding environment needs to be reset.  None: use the `done` of the last step.
-            return_observations: extension — pass False to skip the observation the reference's callers discard
-                (experiments/main.py:227).
-
-        Called with the very `done` the last `step` returned (and nothing in between), the reset is postponed into the
-        next step's launch (module docstring); the observation it returns then comes from the step's launch as well.
-        """
-        if done is None:
-            done = self.done
-        handled, obs = self._try_lazy_reset(done, return_observations)
-        if handled:
-            return obs
-        done = done.view((done.shape[0]))
-        if done.dtype != torch.bool:
-            done = done != 0
-        if done.device != self.device:
-            done = done.to(self.device)
-        return self._reset(done.contiguous(), observe=return_observations)
-
     def _create_envs(self, num_envs: int) -> torch.Tensor:
         """reference :344-387 — a fresh batch of `num_envs` environments (does not touch self.envs)."""
         if self.size <= 8:
@@ -230,64 +189,7 @@ class SingleSnake(FastStepMixin):
         _lib.check(rc, 'SingleSnake._create_envs')
         return envs
 
-    # ------------------------------------------------------------------ fused multi-step loop (extension)
-
-    def rollout(self, actions: torch.Tensor, return_observations: bool = True) -> dict:
-        """T iterations of `obs, r, d, info = env.step(actions[t]); env.reset(d)` in one kernel launch.
-
-        actions: (T, num_envs) int64/int32 on the device, sanitised in place.  Returns a dict of (T, N, ...) tensors
-        (`observations`, `rewards`, `dones`, `self_collision`, `edge_collision`), bit-identical to the Python loop.
-        """
-        if actions.dtype not in (torch.int, torch.long):
-            raise TypeError('actions Tensor must be an integer type i.e. {torch.IntTensor, torch.LongTensor}')
-        if actions.dim() != 2 or actions.shape[1] != self.num_envs:
-            raise RuntimeError('Must have the same number of actions as environments.')
-        if not actions.is_contiguous() or actions.device != self.device:
-            raise RuntimeError('rollout actions must be a contiguous device tensor')
-        T, N = actions.shape
-        if return_observations:
-            m, n, shape = self._mode_info(self.observation_mode)
-            obs = torch.empty((T,) + shape, dtype=torch.float32, device=self.device)
-        else:
-            m, n, obs = _lib.OBS_NONE, 0, None
-        reward = torch.empty((T, N), dtype=torch.float32, device=self.device)
-        flags = torch.empty((3, T, N), dtype=torch.bool, device=self.device)
-        dt = _lib.ACT_I64 if actions.dtype == torch.long else _lib.ACT_I32
-        # Grids of 12 x 12 and larger with a mirror (large batches; round 6): the launch reads the clock grids of the per-call
-        # step instead of the planes and keeps them current, lazy: without writing the planes (wurm_single_rollout_resident).
-        # Same protocol as step(): a postponed reset is applied first, a watched tensor is checked for in-place edits, nothing
-        # is "touched".  (9 x 9 has another mirror format and a launch that costs 11 us besides its steps: the library writes
-        # a lazy mirror out, rolls out on the planes and leaves the mirror stale — what _state() did on this side before.)
-        mirrored = False
-        if T > 0:
-            if self._fs.pending:
-                self._flush()
-            self._mirror_sync()
-            self._setup_mirror(*self._mode_info(self.observation_mode)[:2])
-            mirrored = bool(self._c.resident)
-        if mirrored:
-            c = self._c
-            envs = self._checked(self._envs)
-            self._fs.last_fresh = False
-            self._chk_void_at = self._fs.steps
-            valid = ctypes.c_int(c.resident_valid)
-            rc = _lib.call(self.device.index, _lib.lib().wurm_single_rollout_resident,
-                _lib.ptr(envs), _lib.ptr(actions), dt, _lib.ptr(reward), _lib.ptr(flags[0]), _lib.ptr(flags[1]),
-                _lib.ptr(flags[2]), _lib.ptr(obs), m, n, _lib.i64(N), self.size, _lib.i64(T), _lib.u64(self.seed),
-                _lib.u64(self._next_call(2 * T)), _lib.i64(self.env_offset), c.resident, ctypes.addressof(valid),
-                int(c.resident_lazy), _lib.stream_ptr(self.device.index))
-            c.resident_valid = valid.value if rc == _lib.OK else 0
-        else:
-            envs = self._state()
-            rc = _lib.call(self.device.index, _lib.lib().wurm_single_rollout,
-                _lib.ptr(envs), _lib.ptr(actions), dt,
-                _lib.ptr(reward), _lib.ptr(flags[0]), _lib.ptr(flags[1]), _lib.ptr(flags[2]), _lib.ptr(obs), m, n,
-                _lib.i64(N), self.size, _lib.i64(T), _lib.u64(self.seed), _lib.u64(self._next_call(2 * T)),
-                _lib.i64(self.env_offset), None, None, _lib.stream_ptr(self.device.index))
-        _lib.check(rc, 'SingleSnake.rollout')
-        self._done_all_false()  # every done env was reset
-        return {'observations': obs, 'rewards': reward, 'dones': flags[0], 'self_collision': flags[1],
-                'edge_collision': flags[2]}
+    # ------------------------------------------------------------------ fused acting loop (extension; `rollout`: _fast_step.py)
 
     def policy_rollout(self, params: torch.Tensor, state: torch.Tensor, num_steps: int, check: bool = True) -> dict:
         """T iterations of the acting half of experiments/main.py:207-227 in one kernel launch:
@@ -311,35 +213,7 @@ class SingleSnake(FastStepMixin):
             raise NotImplementedError(f'policy_rollout: partial_{n} crop; the fused actor serves n <= 6')
         if self.size > 64:
             raise NotImplementedError(f'policy_rollout: grid size {self.size}; the fused actor serves sizes up to 64')
-        E = 3 * (2 * n + 1) ** 2 if m == _lib.OBS_PARTIAL else 4
-        N, T = self.num_envs, int(num_steps)
-        if params.dtype != torch.float32 or params.device != self.device or not params.is_contiguous() or \
-                params.numel() != 64 * E + 64 + 64 * 64 + 64 + 4 * 64 + 4 + 64 + 1:
-            raise RuntimeError('params must be the contiguous fp32 device tensor of pack_policy_params for this observation size')
-        if state.device != self.device or state.numel() != N * E:
-            raise RuntimeError('state must be the current observation of every env on the env device')
-        state = state.to(torch.float32).contiguous()
-        envs = self._state()
-        dev = self.device
-        actions = torch.empty((T, N), dtype=torch.long, device=dev)
-        probs = torch.empty((T, N, 4), dtype=torch.float32, device=dev)
-        values = torch.empty((T, N), dtype=torch.float32, device=dev)
-        reward = torch.empty((T, N), dtype=torch.float32, device=dev)
-        flags = torch.empty((3, T, N), dtype=torch.bool, device=dev)
-        obs = torch.empty((T,) + shape, dtype=torch.float32, device=dev)
-        status = torch.empty(N, dtype=torch.uint8, device=dev)
-        rc = _lib.call(dev.index, _lib.lib().wurm_single_policy_rollout_mode,
-                       _lib.ptr(envs), _lib.ptr(state), _lib.ptr(params), _lib.ptr(actions), _lib.ptr(probs),
-                       _lib.ptr(values), _lib.ptr(reward), _lib.ptr(flags[0]), _lib.ptr(flags[1]), _lib.ptr(flags[2]),
-                       _lib.ptr(obs), _lib.ptr(status), m, n, _lib.i64(N), self.size, _lib.i64(T), _lib.u64(self.seed),
-                       _lib.u64(self._next_call(2 * T)), _lib.i64(self.env_offset), _lib.stream_ptr(dev.index))
-        _lib.check(rc, 'SingleSnake.policy_rollout')
-        if check and T > 0 and bool(status.any()):
-            raise RuntimeError('policy_rollout: some envs are not well-formed snakes (status != 0); they were left untouched')
-        self._done_all_false()  # every done env was reset
-        return {'actions': actions, 'probs': probs, 'values': values, 'rewards': reward, 'dones': flags[0],
-                'self_collision': flags[1], 'edge_collision': flags[2], 'observations': obs,
-                'state': obs[-1] if T > 0 else state.reshape(shape), 'status': status}
+        return self._policy_rollout(params, state, num_steps, check, (m, n))
 
     # ------------------------------------------------------------------ invariants
 

@@ -390,16 +390,16 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
     const int my_cell = ly * S + lx;
     const u64 RING = ~lane_mask(lane_in);
     int ex = lane_in ? __float2int_rn(envp[2 * S * S + my_cell]) : 0; // expiry clock of the lane's cell (body, re-read)
-    // carried scalars: head code, orientation * 16, food code (-1: none), the clock T and G = T + length (the length
-    // itself is only ever needed as G - T)
-    int c = uniform(f.hy) * 8 + uniform(f.hx), o16 = uniform(f.o) << 4;
+    // carried scalars: head code, the last move entry (its low 6 bits are orientation * 16), food code (-1: none), the
+    // clock as T1 = T + 1 and G = T + length (the length itself is only ever needed as G - T)
+    int c = uniform(f.hy) * 8 + uniform(f.hx), ent = uniform(f.o) << 4;
     int foodc = -1;
     if (f.food >= 0) {
         const int fy = uniform(div_size(f.food, g.rcpS)); // (float arithmetic: a VALU result, back to an SGPR)
         foodc = fy * 8 + (uniform(f.food) - fy * S);
     }
     u64 XF = RING | (foodc >= 0 ? 1ull << foodc : 0); // ring + food: the non-body cells that make a step eventful
-    int G = uniform(f.L), T = 0;
+    int G = uniform(f.L), T1 = 1;
 
     // partial_n crop: lane owns window cell w (lanes past the window repeat its last cell: same address, same value)
     const int n = OBSK == WURM_OBS_PARTIAL ? p.obs_n : 0, W = 2 * n + 1, W2 = W * W;
@@ -426,22 +426,23 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
         long long my_a = lane < nt ? load_action(p.actions, p.act_dtype, my_t * p.N + env) : 0;
         asm volatile("" : "+v"(my_a)); // retire the load here, not in front of the first readlane of the step loop
         // Moves of step t0 + lane for each of the four orientations the snake may have by then, 16 bits each:
-        // sanitised action (single_snake.py:221-222) & 7 | next orientation << 4 | (code step & 63) << 6, the step
-        // being -TAP[action] (:225-233).  The step loop reads both words with readlanes that do not depend on the
-        // state and picks one with the carried orientation.
+        // next orientation << 4 | (code step & 63) << 6 | (sanitised action (single_snake.py:221-222) & 7) << 12, the
+        // step being -TAP[action] (:225-233); bits 0-3 are zero, so the low 6 bits of an entry are the shift that picks
+        // the NEXT step's entry.  The step loop reads both words with readlanes that do not depend on the state.
         int my_mov01, my_mov23;
         {
+            const auto entry = [](int a_out) {
+                const int ai = a_out & 3;
+                return ((ai ^ 2) << 4) | (((-tap_y(ai) * 8 - tap_x(ai)) & 63) << 6) | ((a_out & 7) << 12);
+            };
             const bool in_range = my_a >= 0 && my_a < 4;
             const int a_small = in_range ? (int)my_a : 7, a_mod = (int)(my_a % 4);
-            int ent[4];
+            int me[4];
 #pragma unroll
-            for (int o = 0; o < 4; ++o) {
-                const int a_out = o == a_small ? (o ^ 2) : a_mod;
-                const int ai = a_out & 3;
-                ent[o] = (a_out & 7) | ((ai ^ 2) << 4) | (((-tap_y(ai) * 8 - tap_x(ai)) & 63) << 6);
-            }
-            my_mov01 = ent[0] | (ent[1] << 16);
-            my_mov23 = ent[2] | (ent[3] << 16);
+            for (int o = 0; o < 4; ++o)
+                me[o] = entry(o == a_small ? (o ^ 2) : a_mod);
+            my_mov01 = me[0] | (me[1] << 16);
+            my_mov23 = me[2] | (me[3] << 16);
         }
         const u64 my_call = p.call + 2ull * (u64)my_t; // step t uses call0 + 2t, its reset call0 + 2t + 1
         S9Reset my_reset;
@@ -469,29 +470,36 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
         // what lane j keeps of step t0 + j: its move entry, whether it ate, self collision | edge collision << 1
         int my_rec = 0, my_ate = 0, my_fl = 0;
         {   // re-base the clocks so that they cannot overflow however long the tape is
+            const int T = T1 - 1;
             ex = max(ex - T, 0);
             G -= T;
-            T = 0;
+            T1 = 1;
         }
 
-        for (int j = 0; j < nt; ++j) {
+        // one step: step t0 + j of this env.  Inlined U + 1 times below (U copies in the unrolled body, one in the tail
+        // loop), each with its own out-of-line event and reset block: the listing holds five of everything in here.
+        const auto step = [&](const int j) __attribute__((always_inline)) {
             // ---- step (single_snake.py:197-304; same line references as step_core / fast_step)
+            // The body after the decay of a step that does not eat, before the head is written and before the move is
+            // known: such a step advances the clock to T1.  A step that eats leaves the clock alone; it takes the
+            // event branch (XF holds the food bit) and looks again there.  (Up here the compare's way to the scalar
+            // unit is covered by the move's scalar instructions.)
+            const u64 body_moved = lane_mask(ex > T1);
             // the two words are the halves of one 64-bit table: entry o is bits [16 o, 16 o + 16)
             const u64 mov = (u64)(u32)lane_value(my_mov01, j) | ((u64)(u32)lane_value(my_mov23, j) << 32);
-            const int ent = (int)(u32)(mov >> o16);
+            ent = (int)(u32)(mov >> (ent & 63));     // (the shift reads the low 6 bits of its amount: no instruction)
             my_rec = set_lane(my_rec, ent, j);       // lane j keeps the record of step t0 + j
-            o16 = ent & 48;
             // c += code step: the head is inside the ring, so the move stays on the grid (in place: left to the compiler, the
             // sum lands in a new register and the plain move pays a copy on the back edge)
             asm("s_add_i32 %0, %0, %1" : "+s"(c) : "s"((ent << 20) >> 26) : "scc");
             G += 1;
-            // T += head != food, through the carry: the clock stands still on the step that eats (:242, :246-249), which
+            // T1 += head != food, through the carry: the clock stands still on the step that eats (:242, :246-249), which
             // is the length growing by one
-            asm("s_cmp_lg_u32 %1, %2\n\ts_addc_u32 %0, %0, 0" : "+s"(T) : "s"(c), "s"(foodc) : "scc");
-            const u64 body = lane_mask(ex > T);      // after the decay, before the head is written
+            asm("s_cmp_lg_u32 %1, %2\n\ts_addc_u32 %0, %0, 0" : "+s"(T1) : "s"(c), "s"(foodc) : "scc");
+            u64 body = body_moved;
             const u64 head = 1ull << (c & 63);
             ex = keep_in_lane(ex, G, head);          // :258-262 (a head on the ring may land in a wrong lane: it is reset below)
-            const u64 occ = body | head;
+            u64 occ = body | head;
 
             // what the crop shows: per lane, is the window cell inside the ring (0 / 1), its code, the occupancy mask
             unsigned inside = 0;
@@ -512,6 +520,12 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
                 const u64 lane_j = 1ull << (j & 63);
                 if (c == foodc) {                    // :270-282: K-th free interior cell in row-major order
                     my_ate = keep_in_lane(my_ate, 1, lane_j);
+                    // The clock stood still (T = T1 - 1): the cell the tail would have left is still body.  `ex` holds
+                    // the head by now, in its own lane (the food cell is inside the ring) and on a cell that was free
+                    // (no food lies on a body cell), so the compare gives the occupancy and the body is that less the head.
+                    occ = lane_mask(ex > T1 - 1);
+                    body = occ & ~head;
+                    mask = occ;
                     if constexpr (INJ) {
                         foodc = lane_value(my_food, j);
                     } else {
@@ -529,7 +543,7 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
                 const int event = ((RING >> (c & 63)) & 1) ? 2 : ((body >> (c & 63)) & 1) ? 1 : 0; // self / edge collision
                 if (OBSK == WURM_OBS_PARTIAL && event == 2) {
                     // the head is on the ring and its code may have wrapped: row / column arithmetic from the cell it left
-                    const int ai = ent & 3, pc = c - ((ent << 20) >> 26);
+                    const int ai = (ent >> 12) & 3, pc = c - ((ent << 20) >> 26);
                     const int hy = (pc >> 3) - tap_y(ai), hx = (pc & 7) - tap_x(ai);
                     inside = max((unsigned)(hy + dy0 - 1), (unsigned)(hx + dx0 - 1)) < 7u ? 1u : 0u;
                     code = (hy + dy0) * 8 + hx + dx0;
@@ -539,13 +553,13 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
                 if (event != 0) {
                     my_fl = keep_in_lane(my_fl, event, lane_j);
                     const int ra = lane_value(my_reset.a, j), rb = lane_value(my_reset.b, j);
-                    o16 = (ra & 3) << 4;
+                    ent = (ra & 3) << 4;             // what is left of the entry: the orientation of the new snake
                     foodc = ra >> 2;
                     XF = INJ ? (RING | (foodc >= 0 ? 1ull << foodc : 0)) : (RING | (1ull << foodc));
                     c = rb & 127;
                     const int sc = (rb >> 7) & 127, tc = rb >> 14;
-                    ex = lane == tc ? T + 1 : 0; ex = lane == sc ? T + 2 : ex; ex = lane == c ? T + 3 : ex;
-                    G = T + 3;                       // length 3
+                    ex = lane == tc ? T1 : 0; ex = lane == sc ? T1 + 1 : ex; ex = lane == c ? T1 + 2 : ex;
+                    G = T1 + 2;                      // T + length 3
                 }
             }
 
@@ -579,10 +593,20 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
                              : : "v"(off_r), "v"(vr), "v"(off_g), "v"(vg), "v"(off_b), "v"(vb), "s"(obs_t) : "memory");
                 obs_t += obs_stride;
             }
+        };
+        // U steps per back edge while the chunk has that many left, then one by one.  The step index stays a scalar that
+        // is advanced per step: the lane selects of the readlanes and of the record take it from a register.
+        constexpr int U = 4; // measured against 2 (1.4 % slower) and 8 (0.5-0.9 % slower): DESIGN.md section 13
+        const int nu = nt & -U;
+        int j = 0;
+        for (; j != nu; j += U) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) step(j + u);
         }
+        for (; j < nt; ++j) step(j);
         if (lane < nt) {
             const long long i = my_t * p.N + env;
-            store_action(p.actions, p.act_dtype, i, (long long)((my_rec << 29) >> 29));
+            store_action(p.actions, p.act_dtype, i, (long long)((my_rec << 17) >> 29));
             p.reward[i] = my_ate ? 1.0f : 0.0f;
             p.done[i] = (uint8_t)(my_fl != 0);
             p.selfc[i] = (uint8_t)(my_fl & 1);
@@ -592,7 +616,7 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
     if (lane_in) { // the ring was empty and still is
         envp[my_cell] = lane == foodc ? 1.0f : 0.0f;
         envp[S * S + my_cell] = lane == c ? 1.0f : 0.0f;
-        envp[2 * S * S + my_cell] = (float)max(ex - T, 0);
+        envp[2 * S * S + my_cell] = (float)max(ex - (T1 - 1), 0);
     }
 }
 

@@ -291,6 +291,18 @@ int wurm_single_policy_rollout_mode(float *envs, const float *obs0, const float 
                                     int64_t num_envs, int size, int64_t num_steps, uint64_t seed, uint64_t call0,
                                     int64_t env_offset, void *stream);
 
+/* wurm_single_policy_rollout_mode for a POPULATION: the num_envs envs are num_members members of M = num_envs /
+ * num_members consecutive envs each, member m owns envs [m M, (m + 1) M) and acts with row m of params
+ * (num_members, num_params), each row packed as above.  Still one launch, the same kernels' arithmetic and the same
+ * routes; every draw is keyed by env_offset + env, so member m's columns of every output and its rows of envs are bit
+ * for bit those of a stand-alone call on its M envs with env_offset + m M.  num_members <= 0 or num_envs % num_members
+ * != 0: WURM_ERR_INVALID_ARG; every other refusal is wurm_single_policy_rollout_mode's.  num_members == 1 is that call. */
+int wurm_single_policy_rollout_pop(float *envs, const float *obs0, const float *params, int64_t *actions, float *probs,
+                                   float *values, float *reward, uint8_t *done, uint8_t *self_collision,
+                                   uint8_t *edge_collision, float *obs, uint8_t *status, int obs_mode, int obs_n,
+                                   int64_t num_envs, int size, int64_t num_steps, uint64_t seed, uint64_t call0,
+                                   int64_t env_offset, void *stream, int64_t num_members);
+
 /* Name of the kernel that served the calling thread's last policy rollout: "policy_s9", "policy_generic" (both
  * policy_rollout.hpp), "policy_wide" (policy_wide.hpp), or "none". */
 const char *wurm_policy_last_route(void);
@@ -335,6 +347,14 @@ int wurm_grid_policy_rollout(float *envs, const float *obs0, const float *params
                              float *values, float *reward, uint8_t *done, uint8_t *edge_collision, float *obs,
                              uint8_t *status, int64_t num_envs, int size, int64_t num_steps, int start_y, int start_x,
                              uint64_t seed, uint64_t call0, int64_t env_offset, void *stream);
+
+/* wurm_grid_policy_rollout for a population: params (num_members, num_params), member m owns the envs
+ * [m M, (m + 1) M), M = num_envs / num_members — as wurm_single_policy_rollout_pop. */
+int wurm_grid_policy_rollout_pop(float *envs, const float *obs0, const float *params, int64_t *actions, float *probs,
+                                 float *values, float *reward, uint8_t *done, uint8_t *edge_collision, float *obs,
+                                 uint8_t *status, int64_t num_envs, int size, int64_t num_steps, int start_y,
+                                 int start_x, uint64_t seed, uint64_t call0, int64_t env_offset, void *stream,
+                                 int64_t num_members);
 
 /* wurm_grid_rollout (RNG mode) for a caller that keeps SimpleGridworld's mirror (wurm_grid_resident_bytes; *resident_valid and
  * resident_lazy as the fields of wurm_single_call): where the one-env-per-lane kernel serves the launch, the state comes from
@@ -659,6 +679,62 @@ int wurm_a2c_ff_update_gae(float *params, const float *obs0, const float *obs, c
                            float *exp_avg, float *exp_avg_sq, float *grad_norm, int64_t step, float lr, float beta1,
                            float beta2, float eps, float max_grad_norm, void *stream, float gamma_lambda,
                            float *returns_out);
+
+/* ------------------------------------------------------------------------------------------- fused A2C population
+ * The calls above for num_members INDEPENDENT agents at once, still three launches: the num_envs envs of the (T,N,.)
+ * inputs are num_members members of M = num_envs / num_members consecutive envs, member m learns from the columns
+ * [m M, (m + 1) M) only (means over its own M T samples) with row m of params / grad / exp_avg / exp_avg_sq
+ * (num_members, P), of losses (num_members, 3) and of grad_norm (num_members).  The grids gain a member dimension; a
+ * member's sub-grid has the workgroups, env ranges, tile order and summation order of a stand-alone call with
+ * num_envs = M, so every result is bit for bit that call's on contiguous copies of the member's columns.
+ *
+ * hyper: DEVICE table (num_members, 4) of doubles — lr, gamma, entropy_coef, gamma_lambda of each member — filled on
+ * the host by wurm_a2c_ff_pop_hyper and copied to the device once by the caller; nothing about the hyper-parameters is
+ * copied or allocated per update.  beta1, beta2, eps, max_grad_norm, value_loss_kind and step are shared.
+ * Refused before any HIP call: null pointers, num_members <= 0, num_envs % num_members != 0 (WURM_ERR_INVALID_ARG),
+ * more than 65535 members (WURM_ERR_UNSUPPORTED), and whatever the stand-alone call refuses for num_envs = M. */
+
+/* num_members times wurm_a2c_ff_workspace_bytes(num_envs / num_members, ...); 0 for an unsupported shape or a
+ * num_envs that num_members does not divide. */
+int64_t wurm_a2c_ff_pop_workspace_bytes(int64_t num_envs, int64_t num_steps, int num_inputs, int64_t num_members);
+
+/* Fills the HOST table (num_members, 4) from host arrays of num_members floats: lr as wurm_a2c_ff_hyper_parameter reads
+ * it (the double a stand-alone apply divides by 1 - beta1^step), the others as the floats they are.  gamma_lambda is
+ * nullable (n-step returns: zeros); as for wurm_a2c_ff_grad_gae each must be finite and >= 0, and each lr >= 0:
+ * anything else is WURM_ERR_INVALID_ARG and the table is not written.  No HIP call. */
+int wurm_a2c_ff_pop_hyper(const float *lr, const float *gamma, const float *entropy_coef, const float *gamma_lambda,
+                          int64_t num_members, double *table);
+
+int wurm_a2c_ff_pop_grad(const float *params, const float *obs0, const float *obs, const int64_t *actions,
+                         const float *rewards, const uint8_t *dones, const double *hyper, int value_loss_kind,
+                         float *grad, float *losses, float *values_out, void *workspace, int64_t workspace_bytes,
+                         int64_t num_envs, int64_t num_steps, int num_inputs, int64_t num_members, void *stream);
+
+int wurm_a2c_ff_pop_grad_gae(const float *params, const float *obs0, const float *obs, const int64_t *actions,
+                             const float *rewards, const uint8_t *dones, const double *hyper, int value_loss_kind,
+                             float *grad, float *losses, float *values_out, void *workspace, int64_t workspace_bytes,
+                             int64_t num_envs, int64_t num_steps, int num_inputs, int64_t num_members, void *stream,
+                             float *returns_out);
+
+/* num_params: of ONE member.  Member m's step size is (float)(hyper[m][0] / (1 - beta1^step)), divided in double on the
+ * device and rounded once, as wurm_a2c_ff_apply rounds it on the host. */
+int wurm_a2c_ff_pop_apply(float *params, const float *grad, float *exp_avg, float *exp_avg_sq, float *grad_norm,
+                          const double *hyper, int64_t step, float beta1, float beta2, float eps, float max_grad_norm,
+                          int64_t num_params, int64_t num_members, void *stream);
+
+int wurm_a2c_ff_pop_update(float *params, const float *obs0, const float *obs, const int64_t *actions,
+                           const float *rewards, const uint8_t *dones, const double *hyper, int value_loss_kind,
+                           float *grad, float *losses, float *values_out, void *workspace, int64_t workspace_bytes,
+                           int64_t num_envs, int64_t num_steps, int num_inputs, int64_t num_members, float *exp_avg,
+                           float *exp_avg_sq, float *grad_norm, int64_t step, float beta1, float beta2, float eps,
+                           float max_grad_norm, void *stream);
+
+int wurm_a2c_ff_pop_update_gae(float *params, const float *obs0, const float *obs, const int64_t *actions,
+                               const float *rewards, const uint8_t *dones, const double *hyper, int value_loss_kind,
+                               float *grad, float *losses, float *values_out, void *workspace, int64_t workspace_bytes,
+                               int64_t num_envs, int64_t num_steps, int num_inputs, int64_t num_members,
+                               float *exp_avg, float *exp_avg_sq, float *grad_norm, int64_t step, float beta1,
+                               float beta2, float eps, float max_grad_norm, void *stream, float *returns_out);
 
 #ifdef __cplusplus
 }

@@ -3,6 +3,7 @@
 //                         every workgroup writes ITS gradient (P floats) and loss sums to the caller's workspace
 //   a2c_ff_reduce_kernel  sums the workgroups' partials in workgroup order into grad / losses
 //   a2c_ff_apply_kernel   ||g|| in a fixed order (every workgroup computes the same bits), clip, Adam
+// and the three with a member dimension in the grid (a2c_ff_main_kernel<GAE, true>, a2c_ff_*_pop_kernel): P updates at once
 // No float atomics anywhere: two runs on the same inputs give the same bits.
 //
 // Main kernel.  A workgroup (256 threads) owns the envs [wg N / G, (wg + 1) N / G) with all T + 1 rows of each (the T
@@ -69,6 +70,21 @@ struct GaeArgs : MainArgs {
 template <bool GAE> struct main_args { using type = MainArgs; };
 template <> struct main_args<true> { using type = GaeArgs; };
 
+// ---- population: P members of M envs each in one grid, blockIdx.y = member.  A member's part of the
+// grid is the grid of a stand-alone update of its M envs — the same G, env ranges, tile and summation order — on pointers
+// moved to its columns and rows, so its bits are those of the stand-alone update.
+constexpr int HYPER_DOUBLES = 4; // a member's row of the hyper-parameter table: lr (as written), gamma, entropy_coef, gamma_lambda
+
+// What the population instantiations take: member 0's pointers; N stays the envs per row of the (T, N, .) tensors, M of
+// them belong to a member; gamma, entropy_coef and gamma_lambda come from the member's row of `hyper`.
+template <class Base> struct PopArgs : Base {
+    const double *hyper; // (P, HYPER_DOUBLES) on the device: floats held exactly, but for lr
+    long long M;
+};
+
+template <bool GAE, bool POP> struct kernel_args { using type = typename main_args<GAE>::type; };
+template <bool GAE> struct kernel_args<GAE, true> { using type = PopArgs<typename main_args<GAE>::type>; };
+
 // acc[i][j] += sum_k A[4 tr + i][k] * B[tj + 16 j][k], k < K (a multiple of 4)
 __device__ __forceinline__ void gemm_nt(const float *A, const float *B, int K, int tr, int tj, float (&acc)[4][4])
 {
@@ -126,8 +142,8 @@ __device__ __forceinline__ float value_loss_derivative(int loss_kind, float dl)
     return 2.0f * dl; // squared error
 }
 
-template <bool GAE>
-__global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(typename main_args<GAE>::type g)
+template <bool GAE, bool POP = false>
+__global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(typename kernel_args<GAE, POP>::type g)
 {
     __shared__ __attribute__((aligned(16))) float Xs[TILE * LD], W1s[HID * LD], W2s[HID * LD], W2Ts[HID * LD];
     __shared__ __attribute__((aligned(16))) float H1s[TILE * LD], H2s[TILE * LD], dZ2s[TILE * LD], dZ1s[TILE * LD];
@@ -138,9 +154,31 @@ __global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(typename main_args
     __shared__ long long row_t[TILE];
 
     const int tid = (int)threadIdx.x, tr = tid >> 4, tj = tid & 15, lane = tid & 63, part = tid >> 6;
-    const long long N = g.N, T = g.T;
+    if constexpr (POP) { // this member's columns, weights, workspace and hyper-parameters; from here on a stand-alone update
+        const long long m = blockIdx.y, first = m * g.M;
+        g.params += m * num_params(g.E);
+        g.obs0 += first * g.E;
+        g.obs += first * g.E;
+        g.actions += first;
+        g.rewards += first;
+        g.dones += first;
+        if (g.values_out != nullptr) g.values_out += first;
+        g.partials += m * g.G * partial_stride(g.E);
+        g.rows += first * (g.T + 1) * ROW_FLOATS;
+        const double *h = g.hyper + m * HYPER_DOUBLES;
+        g.gamma = (float)h[1];
+        g.entropy_coef = (float)h[2];
+        if constexpr (GAE) {
+            g.gamma_lambda = (float)h[3];
+            if (g.returns_out != nullptr) g.returns_out += first;
+        }
+    }
+    const long long N = g.N, T = g.T; // N: envs per row of the inputs
     const int E = g.E, Epad = padded_inputs(E);
-    const long long e0 = (long long)blockIdx.x * N / g.G, e1 = ((long long)blockIdx.x + 1) * N / g.G;
+    long long owned; // the envs the grid's x shares out: all N, or the member's M
+    if constexpr (POP) owned = g.M;
+    else owned = N;
+    const long long e0 = (long long)blockIdx.x * owned / g.G, e1 = ((long long)blockIdx.x + 1) * owned / g.G;
     const long long nenv = e1 - e0, rows = nenv * (T + 1), ntiles = (rows + TILE - 1) / TILE;
     const float *W1 = g.params, *b1 = W1 + 64LL * E, *W2 = b1 + 64, *b2 = W2 + 4096, *Wp = b2 + 64, *bp = Wp + 256,
                 *Wv = bp + 4, *bv = Wv + 64;
@@ -448,9 +486,8 @@ __global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(typename main_args
 }
 
 // grad[i] = sum over the workgroups, in workgroup order; the three loss sums behind it become means
-__global__ __launch_bounds__(THREADS) void a2c_ff_reduce_kernel(const float *__restrict__ partials, int G, int E,
-                                                                float inv_B, float *__restrict__ grad,
-                                                                float *__restrict__ losses)
+__device__ __forceinline__ void a2c_ff_reduce_body(const float *__restrict__ partials, int G, int E, float inv_B,
+                                                   float *__restrict__ grad, float *__restrict__ losses)
 {
     const long long i = (long long)blockIdx.x * THREADS + threadIdx.x, P = num_params(E), stride = partial_stride(E);
     if (i >= P + 3) return;
@@ -465,18 +502,32 @@ __global__ __launch_bounds__(THREADS) void a2c_ff_reduce_kernel(const float *__r
         losses[i - P] = (float)(s * (double)inv_B);
 }
 
+__global__ __launch_bounds__(THREADS) void a2c_ff_reduce_kernel(const float *__restrict__ partials, int G, int E,
+                                                                float inv_B, float *__restrict__ grad,
+                                                                float *__restrict__ losses)
+{
+    a2c_ff_reduce_body(partials, G, E, inv_B, grad, losses);
+}
+
+// member blockIdx.y: its G partials -> its row of grad (P, num_params) and of losses (P, 3)
+__global__ __launch_bounds__(THREADS) void a2c_ff_reduce_pop_kernel(const float *__restrict__ partials, int G, int E,
+                                                                    float inv_B, float *__restrict__ grad,
+                                                                    float *__restrict__ losses)
+{
+    const long long m = blockIdx.y;
+    a2c_ff_reduce_body(partials + m * G * partial_stride(E), G, E, inv_B, grad + m * num_params(E), losses + 3 * m);
+}
+
 constexpr int APPLY_PER_BLOCK = 4 * THREADS;
 
 // Every workgroup forms sum g^2 over ALL of grad in the same order (so they all hold the same bits), then clips and
 // steps its own 1024 parameters.  step_size = lr / (1 - beta1^step), bc2_sqrt = sqrt(1 - beta2^step), w1 = 1 - beta1 and
 // w2 = 1 - beta2 come from the host, computed in double as torch.optim.Adam does.
-__global__ __launch_bounds__(THREADS) void a2c_ff_apply_kernel(float *__restrict__ params,
-                                                               const float *__restrict__ grad,
-                                                               float *__restrict__ exp_avg,
-                                                               float *__restrict__ exp_avg_sq,
-                                                               float *__restrict__ grad_norm, float step_size,
-                                                               float bc2_sqrt, float beta2, float w1, float w2,
-                                                               float eps, float max_norm, long long P)
+__device__ __forceinline__ void a2c_ff_apply_body(float *__restrict__ params, const float *__restrict__ grad,
+                                                  float *__restrict__ exp_avg, float *__restrict__ exp_avg_sq,
+                                                  float *__restrict__ grad_norm, float step_size, float bc2_sqrt,
+                                                  float beta2, float w1, float w2, float eps, float max_norm,
+                                                  long long P)
 {
     __shared__ float red[THREADS];
     const int tid = (int)threadIdx.x;
@@ -505,6 +556,36 @@ __global__ __launch_bounds__(THREADS) void a2c_ff_apply_kernel(float *__restrict
             params[i] = params[i] - step_size * (m / (sqrtf(u) / bc2_sqrt + eps));
         }
     }
+}
+
+__global__ __launch_bounds__(THREADS) void a2c_ff_apply_kernel(float *__restrict__ params,
+                                                               const float *__restrict__ grad,
+                                                               float *__restrict__ exp_avg,
+                                                               float *__restrict__ exp_avg_sq,
+                                                               float *__restrict__ grad_norm, float step_size,
+                                                               float bc2_sqrt, float beta2, float w1, float w2,
+                                                               float eps, float max_norm, long long P)
+{
+    a2c_ff_apply_body(params, grad, exp_avg, exp_avg_sq, grad_norm, step_size, bc2_sqrt, beta2, w1, w2, eps, max_norm, P);
+}
+
+// member blockIdx.y steps its row of the four (P, num_params) buffers with its own learning rate.  step_size is what the
+// host forms for a stand-alone apply, lr / (1 - beta1^step) divided in double and rounded to float once: the table holds
+// lr as the double the host would divide, bc1 is the host's 1 - beta1^step, and the double division and the conversion
+// round to nearest here as they do there.
+__global__ __launch_bounds__(THREADS) void a2c_ff_apply_pop_kernel(float *__restrict__ params,
+                                                                   const float *__restrict__ grad,
+                                                                   float *__restrict__ exp_avg,
+                                                                   float *__restrict__ exp_avg_sq,
+                                                                   float *__restrict__ grad_norm,
+                                                                   const double *__restrict__ hyper, double bc1,
+                                                                   float bc2_sqrt, float beta2, float w1, float w2,
+                                                                   float eps, float max_norm, long long P)
+{
+    const long long m = blockIdx.y, o = m * P;
+    const float step_size = (float)(hyper[m * HYPER_DOUBLES] / bc1);
+    a2c_ff_apply_body(params + o, grad + o, exp_avg + o, exp_avg_sq + o, grad_norm != nullptr ? grad_norm + m : nullptr,
+                      step_size, bc2_sqrt, beta2, w1, w2, eps, max_norm, P);
 }
 
 } // namespace a2c

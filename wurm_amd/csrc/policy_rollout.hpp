@@ -45,6 +45,18 @@ struct PolicyArgs {
     long long env_offset;
 };
 
+// Population: the N envs are members of M consecutive envs each, member m acting with row m of `params`
+// (P, num_params).  The POP instantiations of the kernels take this block and move `params` to the row of their env's member
+// before anything reads it: with one env per wave and the weights in the wave's registers a member is a pointer offset.
+struct PolicyPopArgs : PolicyArgs {
+    long long M;
+};
+
+template <bool POP> struct policy_args { using type = PolicyArgs; };
+template <> struct policy_args<true> { using type = PolicyPopArgs; };
+
+__host__ __device__ inline long long policy_num_params(int E) { return 64LL * E + 64 + 4096 + 64 + 256 + 4 + 64 + 1; }
+
 // the argument block of a policy entry point (self_collision == nullptr: SimpleGridworld, which has no such output)
 static PolicyArgs make_policy_args(float *envs, const float *obs0, const float *params, int64_t *actions, float *probs,
                                    float *values, float *reward, uint8_t *done, uint8_t *self_collision,
@@ -275,13 +287,14 @@ __device__ __forceinline__ void policy_generic_loop(const PolicyArgs &p, long lo
     store_state<CPL, true>(envp, g, e);
 }
 
-template <int NOBS>
+template <int NOBS, bool POP = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NOBS <= 2 ? 2 : 1)))
-void policy_rollout_kernel(PolicyArgs p)
+void policy_rollout_kernel(typename policy_args<POP>::type p)
 {
     constexpr int CPL = 2;
     static_assert(Policy<NOBS>::W2 <= 64, "one window cell per lane");
     const long long env = xcd_block(blockIdx.x, gridDim.x);
+    if constexpr (POP) p.params += env / p.M * policy_num_params(Policy<NOBS>::E);
     const Geo g = make_geo<CPL>(p.S);
     float *envp = p.envs + env * 3 * g.C;
     Env<CPL> e;
@@ -300,12 +313,13 @@ void policy_rollout_kernel(PolicyArgs p)
 // The same loop on the 9x9 machinery of rollout_s9_kernel (single_kernels.hpp: cell codes 8 * row + column, one lane per
 // interior cell, ring / body / food in one bit test, crop liveness from a per-lane table).  Envs that are well formed
 // but outside that kernel's extra preconditions (body or food on the ring) take the generic loop.
-template <int NOBS>
+template <int NOBS, bool POP = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(NOBS <= 2 ? 2 : 1)))
-void policy_rollout_s9_kernel(PolicyArgs p)
+void policy_rollout_s9_kernel(typename policy_args<POP>::type p)
 {
     constexpr int CPL = 2, S = 9, E = Policy<NOBS>::E, W = Policy<NOBS>::W, W2 = Policy<NOBS>::W2;
     const long long env = xcd_block(blockIdx.x, gridDim.x);
+    if constexpr (POP) p.params += env / p.M * policy_num_params(E);
     const Geo g = make_geo<CPL>(S);
     const int lane = g.lane;
     float *envp = p.envs + env * 3 * (S * S);

@@ -11,7 +11,7 @@ namespace wurm {
 thread_local int policy_route = 0;
 
 // the SingleSnake launch (obs_mode WURM_OBS_PARTIAL or WURM_OBS_POSITIONS); arguments already validated
-int launch_policy_wide(const PolicyArgs &p, int obs_mode, int obs_n, void *stream)
+int launch_policy_wide(const PolicyArgs &p, int obs_mode, int obs_n, void *stream, long long members)
 {
     PolicyWideArgs a = {};
     a.p = p;
@@ -19,7 +19,62 @@ int launch_policy_wide(const PolicyArgs &p, int obs_mode, int obs_n, void *strea
     a.obs_n = obs_mode == WURM_OBS_PARTIAL ? obs_n : 0;
     a.E = obs_mode == WURM_OBS_PARTIAL ? 3 * (2 * obs_n + 1) * (2 * obs_n + 1) : 4;
     policy_route = 3;
-    return launch_policy_wide_cpl<true>(a, pick_cpl(p.S), (hipStream_t)stream);
+    return launch_policy_wide_cpl<true>(a, pick_cpl(p.S), (hipStream_t)stream, members);
+}
+
+// single_snake.hip
+int single_policy_rollout(float *envs, const float *obs0, const float *params, int64_t *actions, float *probs,
+                          float *values, float *reward, uint8_t *done, uint8_t *self_collision, uint8_t *edge_collision,
+                          float *obs, uint8_t *status, int obs_n, int64_t num_envs, int size, int64_t num_steps,
+                          uint64_t seed, uint64_t call0, int64_t env_offset, void *stream, long long members);
+
+// wurm_single_policy_rollout_mode (members == 0) and wurm_single_policy_rollout_pop
+static int single_policy_rollout_mode(float *envs, const float *obs0, const float *params, int64_t *actions,
+                                      float *probs, float *values, float *reward, uint8_t *done,
+                                      uint8_t *self_collision, uint8_t *edge_collision, float *obs, uint8_t *status,
+                                      int obs_mode, int obs_n, int64_t num_envs, int size, int64_t num_steps,
+                                      uint64_t seed, uint64_t call0, int64_t env_offset, void *stream, long long members)
+{
+    if (obs_mode == WURM_OBS_PARTIAL)
+        return single_policy_rollout(envs, obs0, params, actions, probs, values, reward, done, self_collision,
+                                     edge_collision, obs, status, obs_n, num_envs, size, num_steps, seed, call0,
+                                     env_offset, stream, members);
+    if (num_envs < 0 || num_steps < 0 || size < 3) return WURM_ERR_INVALID_ARG;
+    // the image modes: the reference's FeedforwardAgent takes a flat vector (experiments/main.py:129-137 builds it for
+    // 'positions' and 'partial_n' only); WURM_OBS_NONE leaves the policy nothing to act on
+    if (obs_mode != WURM_OBS_POSITIONS) return WURM_ERR_UNSUPPORTED;
+    if (size <= 8 || size > 64) return WURM_ERR_UNSUPPORTED; // the reset draw needs 9 x 9; 64 x 64 is the largest grid
+    if (num_envs == 0 || num_steps == 0) return WURM_OK;
+    if (!envs || !obs0 || !params || !actions || !probs || !values || !reward || !done || !self_collision ||
+        !edge_collision || !obs || !status)
+        return WURM_ERR_INVALID_ARG;
+    const PolicyArgs p = make_policy_args(envs, obs0, params, actions, probs, values, reward, done, self_collision,
+                                          edge_collision, obs, status, num_envs, size, num_steps, seed, call0, env_offset);
+    return launch_policy_wide(p, WURM_OBS_POSITIONS, 0, stream, members);
+}
+
+// wurm_grid_policy_rollout (members == 0) and wurm_grid_policy_rollout_pop
+static int grid_policy_rollout(float *envs, const float *obs0, const float *params, int64_t *actions, float *probs,
+                               float *values, float *reward, uint8_t *done, uint8_t *edge_collision, float *obs,
+                               uint8_t *status, int64_t num_envs, int size, int64_t num_steps, int start_y, int start_x,
+                               uint64_t seed, uint64_t call0, int64_t env_offset, void *stream, long long members)
+{
+    if (num_envs < 0 || num_steps < 0 || size < 3) return WURM_ERR_INVALID_ARG;
+    if (size <= 4 || size > 64) return WURM_ERR_UNSUPPORTED; // simple_gridworld.py:249-250; 64 x 64 is the largest grid
+    if (start_y < 0 || start_x < 0 || start_y >= size || start_x >= size) return WURM_ERR_UNSUPPORTED;
+    if (num_envs == 0 || num_steps == 0) return WURM_OK;
+    if (!envs || !obs0 || !params || !actions || !probs || !values || !reward || !done || !edge_collision || !obs ||
+        !status)
+        return WURM_ERR_INVALID_ARG;
+    PolicyWideArgs a = {};
+    a.p = make_policy_args(envs, obs0, params, actions, probs, values, reward, done, nullptr, edge_collision, obs, status,
+                           num_envs, size, num_steps, seed, call0, env_offset);
+    a.obs_mode = WURM_OBS_POSITIONS;
+    a.E = 4;
+    a.start_y = start_y;
+    a.start_x = start_x;
+    policy_route = 3;
+    return launch_policy_wide_cpl<false>(a, pick_cpl(size), (hipStream_t)stream, members);
 }
 
 } // namespace wurm
@@ -44,22 +99,21 @@ int wurm_single_policy_rollout_mode(float *envs, const float *obs0, const float 
                                     int64_t num_envs, int size, int64_t num_steps, uint64_t seed, uint64_t call0,
                                     int64_t env_offset, void *stream)
 {
-    if (obs_mode == WURM_OBS_PARTIAL)
-        return wurm_single_policy_rollout(envs, obs0, params, actions, probs, values, reward, done, self_collision,
-                                          edge_collision, obs, status, obs_n, num_envs, size, num_steps, seed, call0,
-                                          env_offset, stream);
-    if (num_envs < 0 || num_steps < 0 || size < 3) return WURM_ERR_INVALID_ARG;
-    // the image modes: the reference's FeedforwardAgent takes a flat vector (experiments/main.py:129-137 builds it for
-    // 'positions' and 'partial_n' only); WURM_OBS_NONE leaves the policy nothing to act on
-    if (obs_mode != WURM_OBS_POSITIONS) return WURM_ERR_UNSUPPORTED;
-    if (size <= 8 || size > 64) return WURM_ERR_UNSUPPORTED; // the reset draw needs 9 x 9; 64 x 64 is the largest grid
-    if (num_envs == 0 || num_steps == 0) return WURM_OK;
-    if (!envs || !obs0 || !params || !actions || !probs || !values || !reward || !done || !self_collision ||
-        !edge_collision || !obs || !status)
-        return WURM_ERR_INVALID_ARG;
-    const PolicyArgs p = make_policy_args(envs, obs0, params, actions, probs, values, reward, done, self_collision,
-                                          edge_collision, obs, status, num_envs, size, num_steps, seed, call0, env_offset);
-    return launch_policy_wide(p, WURM_OBS_POSITIONS, 0, stream);
+    return single_policy_rollout_mode(envs, obs0, params, actions, probs, values, reward, done, self_collision,
+                                      edge_collision, obs, status, obs_mode, obs_n, num_envs, size, num_steps, seed,
+                                      call0, env_offset, stream, 0);
+}
+
+int wurm_single_policy_rollout_pop(float *envs, const float *obs0, const float *params, int64_t *actions, float *probs,
+                                   float *values, float *reward, uint8_t *done, uint8_t *self_collision,
+                                   uint8_t *edge_collision, float *obs, uint8_t *status, int obs_mode, int obs_n,
+                                   int64_t num_envs, int size, int64_t num_steps, uint64_t seed, uint64_t call0,
+                                   int64_t env_offset, void *stream, int64_t num_members)
+{
+    if (num_members <= 0 || num_envs % num_members != 0) return WURM_ERR_INVALID_ARG;
+    return single_policy_rollout_mode(envs, obs0, params, actions, probs, values, reward, done, self_collision,
+                                      edge_collision, obs, status, obs_mode, obs_n, num_envs, size, num_steps, seed,
+                                      call0, env_offset, stream, num_members);
 }
 
 int wurm_grid_policy_rollout(float *envs, const float *obs0, const float *params, int64_t *actions, float *probs,
@@ -67,22 +121,19 @@ int wurm_grid_policy_rollout(float *envs, const float *obs0, const float *params
                              uint8_t *status, int64_t num_envs, int size, int64_t num_steps, int start_y, int start_x,
                              uint64_t seed, uint64_t call0, int64_t env_offset, void *stream)
 {
-    if (num_envs < 0 || num_steps < 0 || size < 3) return WURM_ERR_INVALID_ARG;
-    if (size <= 4 || size > 64) return WURM_ERR_UNSUPPORTED; // simple_gridworld.py:249-250; 64 x 64 is the largest grid
-    if (start_y < 0 || start_x < 0 || start_y >= size || start_x >= size) return WURM_ERR_UNSUPPORTED;
-    if (num_envs == 0 || num_steps == 0) return WURM_OK;
-    if (!envs || !obs0 || !params || !actions || !probs || !values || !reward || !done || !edge_collision || !obs ||
-        !status)
-        return WURM_ERR_INVALID_ARG;
-    PolicyWideArgs a = {};
-    a.p = make_policy_args(envs, obs0, params, actions, probs, values, reward, done, nullptr, edge_collision, obs, status,
-                           num_envs, size, num_steps, seed, call0, env_offset);
-    a.obs_mode = WURM_OBS_POSITIONS;
-    a.E = 4;
-    a.start_y = start_y;
-    a.start_x = start_x;
-    policy_route = 3;
-    return launch_policy_wide_cpl<false>(a, pick_cpl(size), (hipStream_t)stream);
+    return grid_policy_rollout(envs, obs0, params, actions, probs, values, reward, done, edge_collision, obs, status,
+                               num_envs, size, num_steps, start_y, start_x, seed, call0, env_offset, stream, 0);
+}
+
+int wurm_grid_policy_rollout_pop(float *envs, const float *obs0, const float *params, int64_t *actions, float *probs,
+                                 float *values, float *reward, uint8_t *done, uint8_t *edge_collision, float *obs,
+                                 uint8_t *status, int64_t num_envs, int size, int64_t num_steps, int start_y,
+                                 int start_x, uint64_t seed, uint64_t call0, int64_t env_offset, void *stream,
+                                 int64_t num_members)
+{
+    if (num_members <= 0 || num_envs % num_members != 0) return WURM_ERR_INVALID_ARG;
+    return grid_policy_rollout(envs, obs0, params, actions, probs, values, reward, done, edge_collision, obs, status,
+                               num_envs, size, num_steps, start_y, start_x, seed, call0, env_offset, stream, num_members);
 }
 
 } // extern "C"

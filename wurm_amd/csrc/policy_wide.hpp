@@ -36,6 +36,18 @@ struct PolicyWideArgs {
     int wpb, wave_bytes; // waves per workgroup, LDS bytes per wave
 };
 
+// What the POP instantiations take (policy_rollout.hpp: PolicyPopArgs).  A workgroup copies W1 into LDS once for all its
+// waves, so it must not hold envs of two members: the grid is wgpm = ceil(M / wpb) workgroups PER MEMBER, member-major,
+// workgroup i of a member holds its envs [i wpb, (i + 1) wpb) and the waves past the member's last env leave — for any M,
+// M = 1 and M prime included.
+struct PolicyWidePopArgs : PolicyWideArgs {
+    long long M;
+    unsigned wgpm;
+};
+
+template <bool POP> struct policy_wide_args { using type = PolicyWideArgs; };
+template <> struct policy_wide_args<true> { using type = PolicyWidePopArgs; };
+
 // the policy of one wave with the first layer in LDS
 struct PolicyWide : PolicyHead {
     const f2 *w1;   // LDS: (EP / 2, 64) pairs, shared by the workgroup
@@ -95,10 +107,18 @@ __device__ __forceinline__ void fast_positions(const Geo &g, const Fast &f, floa
 template <int CPL>
 constexpr int policy_wide_max_wpb() { return CPL >= 48 ? 4 : 8; }
 
-template <int CPL, bool SNAKE>
-__global__ __launch_bounds__(64 * policy_wide_max_wpb<CPL>()) void policy_wide_kernel(PolicyWideArgs a)
+template <int CPL, bool SNAKE, bool POP = false>
+__global__ __launch_bounds__(64 * policy_wide_max_wpb<CPL>())
+void policy_wide_kernel(typename policy_wide_args<POP>::type a)
 {
     typedef PolicyWide::f2 f2;
+    long long pop_first = 0, pop_wg = 0; // POP: the member's first env, the workgroup's place among the member's
+    if constexpr (POP) {
+        const long long wg = xcd_block(blockIdx.x, gridDim.x), member = wg / a.wgpm;
+        pop_wg = wg - member * a.wgpm;
+        pop_first = member * a.M;
+        a.p.params += member * policy_num_params(a.E);
+    }
     const PolicyArgs &p = a.p;
     const int E = a.E, EP = a.EP;
     {   // W1 (64, E) -> LDS as (EP / 2, 64) pairs, zero padded: input k of unit j at float 128 (k / 2) + 2 j + (k & 1).
@@ -117,8 +137,15 @@ __global__ __launch_bounds__(64 * policy_wide_max_wpb<CPL>()) void policy_wide_k
     }
     __syncthreads();
     const int wave = uniform((int)(threadIdx.x >> 6));
-    const long long env = xcd_block(blockIdx.x, gridDim.x) * a.wpb + wave;
-    if (env >= p.N) return;
+    long long env;
+    if constexpr (POP) {
+        const long long i = pop_wg * a.wpb + wave;
+        if (i >= a.M) return;
+        env = pop_first + i;
+    } else {
+        env = xcd_block(blockIdx.x, gridDim.x) * a.wpb + wave;
+        if (env >= p.N) return;
+    }
     signed char *wl = wurm_lds + (size_t)EP * 256 + (size_t)wave * a.wave_bytes;
     float *x = (float *)wl;
     signed char *cls = wl + (size_t)EP * 4 + 256; // write_obs's class map (crops of grids > 128 cells)
@@ -188,8 +215,9 @@ __global__ __launch_bounds__(64 * policy_wide_max_wpb<CPL>()) void policy_wide_k
     store_state<CPL, SNAKE>(envp, g, e);
 }
 
+// members == 0: the N envs act with one set of weights; members >= 1: a population of that many members (N % members == 0)
 template <bool SNAKE>
-static int launch_policy_wide_cpl(PolicyWideArgs a, int cpl, hipStream_t st)
+static int launch_policy_wide_cpl(PolicyWideArgs a, int cpl, hipStream_t st, long long members = 0)
 {
     constexpr int LDS_MAX = 160 * 1024, W1_LDS_PER_INPUT = 64 * 4;
     const int S = a.p.S;
@@ -206,6 +234,33 @@ static int launch_policy_wide_cpl(PolicyWideArgs a, int cpl, hipStream_t st)
         WURM_LAUNCH(kernel, grid, block, lds, st, a);
     };
     (void)hipGetLastError();
+    if (members > 0) {
+        PolicyWidePopArgs b = {};
+        static_cast<PolicyWideArgs &>(b) = a;
+        b.M = a.p.N / members;
+        b.wpb = (int)std::min((long long)a.wpb, b.M); // (no workgroup of idle waves only)
+        b.wgpm = (unsigned)((b.M + b.wpb - 1) / b.wpb);
+        const size_t lds_pop = (size_t)a.EP * W1_LDS_PER_INPUT + (size_t)b.wpb * a.wave_bytes;
+        block = dim3(64 * b.wpb);
+        grid = dim3((unsigned)(members * b.wgpm));
+        auto go_pop = [&](auto kernel) {
+            if (lds_pop > 65536)
+                (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pop);
+            WURM_LAUNCH(kernel, grid, block, lds_pop, st, b);
+        };
+        switch (cpl) {
+        case 2: go_pop(policy_wide_kernel<2, SNAKE, true>); break;
+        case 4: go_pop(policy_wide_kernel<4, SNAKE, true>); break;
+        case 8: go_pop(policy_wide_kernel<8, SNAKE, true>); break;
+        case 16: go_pop(policy_wide_kernel<16, SNAKE, true>); break;
+        case 24: go_pop(policy_wide_kernel<24, SNAKE, true>); break;
+        case 32: go_pop(policy_wide_kernel<32, SNAKE, true>); break;
+        case 48: go_pop(policy_wide_kernel<48, SNAKE, true>); break;
+        case 64: go_pop(policy_wide_kernel<64, SNAKE, true>); break;
+        default: return WURM_ERR_UNSUPPORTED;
+        }
+        return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+    }
     switch (cpl) {
     case 2: go(policy_wide_kernel<2, SNAKE>); break;
     case 4: go(policy_wide_kernel<4, SNAKE>); break;

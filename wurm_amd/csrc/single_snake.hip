@@ -126,11 +126,12 @@ static int launch_gridworld_on_mirror(Kind kind, StepArgs p, void *resident, int
     }
 
 // policy_wide.hip: the fused actor beyond policy_rollout.hpp's domain, and the route of the last policy launch
-int launch_policy_wide(const PolicyArgs &p, int obs_mode, int obs_n, void *stream);
+// (members == 0: one set of weights; members >= 1: a population, params (members, num_params), p.N % members == 0)
+int launch_policy_wide(const PolicyArgs &p, int obs_mode, int obs_n, void *stream, long long members);
 extern thread_local int policy_route;
 
 // the fused actor on policy_rollout.hpp's domain (S <= 11, partial_n with n <= 3); arguments already validated
-static int launch_policy_rollout(const PolicyArgs &p, int obs_n, void *stream)
+static int launch_policy_rollout(const PolicyArgs &p, int obs_n, void *stream, long long members)
 {
     const int W2 = (2 * obs_n + 1) * (2 * obs_n + 1), EP = (3 * W2 + 3) & ~3;
     const size_t lds = (size_t)(EP + 64) * sizeof(float);
@@ -142,6 +143,23 @@ static int launch_policy_rollout(const PolicyArgs &p, int obs_n, void *stream)
         if (s9) WURM_LAUNCH(s9_kernel, grid, block, lds, st, p);
         else WURM_LAUNCH(kernel, grid, block, lds, st, p);
     };
+    if (members > 0) {
+        PolicyPopArgs pp = {};
+        static_cast<PolicyArgs &>(pp) = p;
+        pp.M = p.N / members;
+        auto go_pop = [&](auto s9_kernel, auto kernel) {
+            if (s9) WURM_LAUNCH(s9_kernel, grid, block, lds, st, pp);
+            else WURM_LAUNCH(kernel, grid, block, lds, st, pp);
+        };
+        switch (obs_n) {
+        case 0: go_pop(policy_rollout_s9_kernel<0, true>, policy_rollout_kernel<0, true>); break;
+        case 1: go_pop(policy_rollout_s9_kernel<1, true>, policy_rollout_kernel<1, true>); break;
+        case 2: go_pop(policy_rollout_s9_kernel<2, true>, policy_rollout_kernel<2, true>); break;
+        case 3: go_pop(policy_rollout_s9_kernel<3, true>, policy_rollout_kernel<3, true>); break;
+        default: return WURM_ERR_UNSUPPORTED;
+        }
+        return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+    }
     switch (obs_n) {
     case 0: go(policy_rollout_s9_kernel<0>, policy_rollout_kernel<0>); break;
     case 1: go(policy_rollout_s9_kernel<1>, policy_rollout_kernel<1>); break;
@@ -150,6 +168,27 @@ static int launch_policy_rollout(const PolicyArgs &p, int obs_n, void *stream)
     default: return WURM_ERR_UNSUPPORTED;
     }
     return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+}
+
+// wurm_single_policy_rollout (members == 0) and the WURM_OBS_PARTIAL half of wurm_single_policy_rollout_pop
+int single_policy_rollout(float *envs, const float *obs0, const float *params, int64_t *actions, float *probs,
+                          float *values, float *reward, uint8_t *done, uint8_t *self_collision, uint8_t *edge_collision,
+                          float *obs, uint8_t *status, int obs_n, int64_t num_envs, int size, int64_t num_steps,
+                          uint64_t seed, uint64_t call0, int64_t env_offset, void *stream, long long members)
+{
+    if (num_envs < 0 || num_steps < 0 || size < 3) return WURM_ERR_INVALID_ARG;
+    // the reset draw needs 9 x 9; 64 x 64 is the largest grid; n <= 6 is what the crop machinery covers (CROP_NI)
+    if (size <= 8 || size > 64 || obs_n < 0 || obs_n > 6) return WURM_ERR_UNSUPPORTED;
+    if (num_envs == 0 || num_steps == 0) return WURM_OK;
+    if (!envs || !obs0 || !params || !actions || !probs || !values || !reward || !done || !self_collision ||
+        !edge_collision || !obs || !status)
+        return WURM_ERR_INVALID_ARG;
+    const PolicyArgs p = make_policy_args(envs, obs0, params, actions, probs, values, reward, done, self_collision,
+                                          edge_collision, obs, status, num_envs, size, num_steps, seed, call0, env_offset);
+    // policy_rollout.hpp's kernels on their domain (WURM_POLICY_WIDE = 1 moves it to policy_wide_kernel), policy_wide.hpp beyond
+    if (size > 11 || obs_n > 3 || opt.policy_wide) return launch_policy_wide(p, WURM_OBS_PARTIAL, obs_n, stream, members);
+    policy_route = size == 9 && !opt.policy_generic ? 1 : 2;
+    return launch_policy_rollout(p, obs_n, stream, members);
 }
 
 } // namespace wurm
@@ -411,19 +450,8 @@ int wurm_single_policy_rollout(float *envs, const float *obs0, const float *para
                                int size, int64_t num_steps, uint64_t seed, uint64_t call0, int64_t env_offset,
                                void *stream)
 {
-    if (num_envs < 0 || num_steps < 0 || size < 3) return WURM_ERR_INVALID_ARG;
-    // the reset draw needs 9 x 9; 64 x 64 is the largest grid; n <= 6 is what the crop machinery covers (CROP_NI)
-    if (size <= 8 || size > 64 || obs_n < 0 || obs_n > 6) return WURM_ERR_UNSUPPORTED;
-    if (num_envs == 0 || num_steps == 0) return WURM_OK;
-    if (!envs || !obs0 || !params || !actions || !probs || !values || !reward || !done || !self_collision ||
-        !edge_collision || !obs || !status)
-        return WURM_ERR_INVALID_ARG;
-    const PolicyArgs p = make_policy_args(envs, obs0, params, actions, probs, values, reward, done, self_collision,
-                                          edge_collision, obs, status, num_envs, size, num_steps, seed, call0, env_offset);
-    // policy_rollout.hpp's kernels on their domain (WURM_POLICY_WIDE = 1 moves it to policy_wide_kernel), policy_wide.hpp beyond
-    if (size > 11 || obs_n > 3 || opt.policy_wide) return launch_policy_wide(p, WURM_OBS_PARTIAL, obs_n, stream);
-    policy_route = size == 9 && !opt.policy_generic ? 1 : 2;
-    return launch_policy_rollout(p, obs_n, stream);
+    return single_policy_rollout(envs, obs0, params, actions, probs, values, reward, done, self_collision, edge_collision,
+                                 obs, status, obs_n, num_envs, size, num_steps, seed, call0, env_offset, stream, 0);
 }
 
 int wurm_single_check(const float *envs, uint32_t *err, int64_t num_envs, int size, void *stream)

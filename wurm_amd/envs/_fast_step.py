@@ -789,13 +789,24 @@ class FastStepMixin(object):
         self._done_all_false()  # every done env was reset
         return dict(observations=obs, rewards=reward, **dict(zip(self._FLAG_KEYS, flags)))
 
-    def _policy_rollout(self, params: torch.Tensor, state: torch.Tensor, num_steps: int, check: bool, mode_args: tuple) -> dict:
+    def _policy_rollout(self, params: torch.Tensor, state: torch.Tensor, num_steps: int, check: bool, mode_args: tuple,
+                        population: int = None) -> dict:
         """What the classes' policy_rollout share once their preconditions hold (mode_args: what the class's entry point
-        takes between `status` and the batch size)."""
+        takes between `status` and the batch size).  population: None, or the number of members P — params is then
+        (P, num_params) and member p acts in the envs [p N / P, (p + 1) N / P) (the entry point _POLICY_POP_FN)."""
         shape = self._mode_info(self.observation_mode)[2]
         N, T, E = self.num_envs, int(num_steps), int(torch.Size(shape[1:]).numel())
-        if params.dtype != torch.float32 or params.device != self.device or not params.is_contiguous() or \
-                params.numel() != 64 * E + 64 + 64 * 64 + 64 + 4 * 64 + 4 + 64 + 1:
+        num_params = 64 * E + 64 + 64 * 64 + 64 + 4 * 64 + 4 + 64 + 1
+        if population is not None:  # (argument errors first: nothing below touches the library before them)
+            P = int(population)
+            if P <= 0 or N % P != 0:
+                raise RuntimeError(f'population must be a positive divisor of num_envs ({N}), got {population}')
+            if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or params.device != self.device or \
+                    not params.is_contiguous() or tuple(params.shape) != (P, num_params):
+                raise RuntimeError(f'params must be a contiguous fp32 ({P}, {num_params}) device tensor: one row of '
+                                   f'pack_policy_params per member')
+        elif params.dtype != torch.float32 or params.device != self.device or not params.is_contiguous() or \
+                params.numel() != num_params:
             raise RuntimeError('params must be the contiguous fp32 device tensor of pack_policy_params for this observation size')
         if state.device != self.device or state.numel() != N * E:
             raise RuntimeError('state must be the current observation of every env on the env device')
@@ -809,11 +820,12 @@ class FastStepMixin(object):
         flags = torch.empty((len(self._FLAG_KEYS), T, N), dtype=torch.bool, device=dev).unbind(0)
         obs = torch.empty((T,) + tuple(shape), dtype=torch.float32, device=dev)
         status = torch.empty(N, dtype=torch.uint8, device=dev)
-        rc = _lib.call(dev.index, getattr(_lib.lib(), self._POLICY_FN),
+        members = () if population is None else (_lib.i64(population),)
+        rc = _lib.call(dev.index, getattr(_lib.lib(), self._POLICY_FN if population is None else self._POLICY_POP_FN),
                        _lib.ptr(envs), _lib.ptr(state), _lib.ptr(params), _lib.ptr(actions), _lib.ptr(probs),
                        _lib.ptr(values), _lib.ptr(reward), *[_lib.ptr(f) for f in flags], _lib.ptr(obs), _lib.ptr(status),
                        *mode_args, _lib.i64(N), self.size, _lib.i64(T), *self._start_args(), _lib.u64(self.seed),
-                       _lib.u64(self._next_call(2 * T)), _lib.i64(self.env_offset), _lib.stream_ptr(dev.index))
+                       _lib.u64(self._next_call(2 * T)), _lib.i64(self.env_offset), _lib.stream_ptr(dev.index), *members)
         _lib.check(rc, self._NAME + '.policy_rollout')
         if check and T > 0 and bool(status.any()):
             raise RuntimeError(f'policy_rollout: {self._BAD_STATUS} (status != 0); they were left untouched')

@@ -24,6 +24,7 @@ class SimpleGridworld(FastStepMixin):
     _STEP_SLOT = 'wurm_grid_step_slot'
     _ROLLOUT_FNS = ('wurm_grid_rollout', 'wurm_grid_rollout_resident')
     _POLICY_FN = 'wurm_grid_policy_rollout'
+    _POLICY_POP_FN = 'wurm_grid_policy_rollout_pop'
     _FLAG_KEYS = ('dones', 'edge_collision')
     _BAD_STATUS = 'some envs do not hold exactly one agent and one food'
     _RESIDENT_FNS = ('wurm_grid_resident_bytes', 'wurm_grid_resident_size', 'wurm_grid_resident_flush')
@@ -151,13 +152,15 @@ class SimpleGridworld(FastStepMixin):
     def _make_out(self, i: int):
         return self._v_obs[i], self._v_reward[i], self._v_done2[i], {'edge_collision': self._v_edgec[i]}
 
-    def policy_rollout(self, params: torch.Tensor, state: torch.Tensor, num_steps: int, check: bool = True) -> dict:
+    def policy_rollout(self, params: torch.Tensor, state: torch.Tensor, num_steps: int, check: bool = True,
+                       population: int = None) -> dict:
         """T iterations of `probs, value = model(state); action = Categorical(probs).sample(); state, reward, done, info =
         env.step(action); env.reset(done)` in one kernel launch (see SingleSnake.policy_rollout).  The env must be in
         'positions' mode (the reference's feed-forward agent takes a flat observation; experiments/main.py:129-137) with a
         start location.  params: `pack_policy_params` of an agent with 4 inputs; state: (num_envs, 4).  Returns (T, N, ...)
         tensors `actions`, `probs`, `values`, `rewards`, `dones`, `edge_collision`, `observations`, and `state`, `status`.
-        `check=True` synchronises once and raises if any env did not hold exactly one agent and one food."""
+        `check=True` synchronises once and raises if any env did not hold exactly one agent and one food.
+        population=P: P policies, `params` (P, num_params), member p in the envs [p N / P, (p + 1) N / P) (see SingleSnake)."""
         if self.observation_mode != 'positions':
             raise NotImplementedError(f'policy_rollout: observation mode {self.observation_mode!r} is an image; the '
                                       f"feed-forward agent takes 'positions' observations")
@@ -165,7 +168,7 @@ class SimpleGridworld(FastStepMixin):
             raise NotImplementedError("Haven't implemented random starting locations")
         if self.size <= 4 or self.size > 64:
             raise NotImplementedError(f'policy_rollout: grid size {self.size}; the fused actor serves sizes 5 to 64')
-        return self._policy_rollout(params, state, num_steps, check, ())
+        return self._policy_rollout(params, state, num_steps, check, (), population)
 
     def _consistent(self):
         pass

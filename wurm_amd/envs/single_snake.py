@@ -39,6 +39,7 @@ class SingleSnake(FastStepMixin):
     _STEP_SLOT = 'wurm_single_step_slot'
     _ROLLOUT_FNS = ('wurm_single_rollout', 'wurm_single_rollout_resident')
     _POLICY_FN = 'wurm_single_policy_rollout_mode'
+    _POLICY_POP_FN = 'wurm_single_policy_rollout_pop'
     _FLAG_KEYS = ('dones', 'self_collision', 'edge_collision')
     _BAD_STATUS = 'some envs are not well-formed snakes'
     _EMPTY_ROLLOUT_SKIPS_MIRROR = True   # rollout(): no steps, no look at the mirror (9 x 9's is not the rollout's anyway)
@@ -191,7 +192,8 @@ class SingleSnake(FastStepMixin):
 
     # ------------------------------------------------------------------ fused acting loop (extension; `rollout`: _fast_step.py)
 
-    def policy_rollout(self, params: torch.Tensor, state: torch.Tensor, num_steps: int, check: bool = True) -> dict:
+    def policy_rollout(self, params: torch.Tensor, state: torch.Tensor, num_steps: int, check: bool = True,
+                       population: int = None) -> dict:
         """T iterations of the acting half of experiments/main.py:207-227 in one kernel launch:
 
             probs, value = model(state); action = Categorical(probs).sample()
@@ -204,7 +206,12 @@ class SingleSnake(FastStepMixin):
         `probs`, `values` (no grad — the learner recomputes them from `observations`), `rewards`, `dones`,
         `self_collision`, `edge_collision`, `observations` (what step t returned, i.e. the policy input of step t+1)
         and `state` = observations[-1].  `check=True` synchronises once and raises if any env was outside the
-        kernel's domain (not a well-formed snake — only possible if `env.envs` was edited by hand)."""
+        kernel's domain (not a well-formed snake — only possible if `env.envs` was edited by hand).
+
+        population=P (extension): P independent policies in the same launch.  The envs are P members of num_envs / P
+        consecutive envs each; member p acts with `params[p]` of a contiguous fp32 (P, num_params) tensor (RuntimeError
+        otherwise, or if P does not divide num_envs).  Same keys and shapes; member p's columns are bit for bit what a
+        stand-alone env of its envs (`env_offset` + p num_envs / P, the same seed and call count) returns."""
         m, n, shape = self._mode_info(self.observation_mode)
         if m not in (_lib.OBS_PARTIAL, _lib.OBS_POSITIONS):
             raise NotImplementedError(f'policy_rollout: observation mode {self.observation_mode!r} is an image; the '
@@ -213,7 +220,7 @@ class SingleSnake(FastStepMixin):
             raise NotImplementedError(f'policy_rollout: partial_{n} crop; the fused actor serves n <= 6')
         if self.size > 64:
             raise NotImplementedError(f'policy_rollout: grid size {self.size}; the fused actor serves sizes up to 64')
-        return self._policy_rollout(params, state, num_steps, check, (m, n))
+        return self._policy_rollout(params, state, num_steps, check, (m, n), population)
 
     # ------------------------------------------------------------------ invariants
 

@@ -5,6 +5,10 @@ kernel, as in examples/a2c_fused_actor.py), the learning half is `learner.update
 backward pass, clip_grad_norm_ and Adam in three launches (wurm_amd.rl.FusedA2CLearner).  Per update the host issues four
 kernel launches and reads nothing back; the loss is copied to the host only for a log line.  `--gae-lambda` switches the
 returns from n-step to generalised advantage estimation (the reference's `--gae-lambda`), still in the same launches.
+The log line has the reference's columns (main.py:252-316: episodes, reward_rate, policy_entropy, edge_collisions,
+self_collisions, avg_size and their smoothed `ewm_` versions) and the mean and maximum return, length and final snake
+size of the episodes that ended since the last line: `wurm_amd.rl.RolloutStats` keeps them on the device, two more
+launches per window, and is read once per line.
 
     python examples/a2c_fused_learner.py --num-envs 512 --steps 20000
     python examples/a2c_fused_learner.py --num-envs 512 --steps 20000 --gae-lambda 0.95
@@ -19,7 +23,7 @@ import torch  # noqa: E402
 
 from wurm_amd.agents import FeedforwardAgent  # noqa: E402
 from wurm_amd.envs import SingleSnake  # noqa: E402
-from wurm_amd.rl import FusedA2CLearner  # noqa: E402
+from wurm_amd.rl import FusedA2CLearner, RolloutStats  # noqa: E402
 
 
 def run(num_envs=512, size=9, observation='partial_2', steps=20000, update_steps=5, gamma=0.99, lr=1e-3, entropy=0.01,
@@ -30,21 +34,19 @@ def run(num_envs=512, size=9, observation='partial_2', steps=20000, update_steps
     model = FeedforwardAgent(num_actions=4, num_layers=2, hidden_units=64, num_inputs=state[0].numel()).to(device)
     learner = FusedA2CLearner(model, lr=lr, gamma=gamma, entropy_coef=entropy, max_grad_norm=0.5,
                               use_gae=gae_lambda is not None, gae_lambda=gae_lambda)        # multiagent.py:274-275
-    totals = torch.zeros(2, dtype=torch.float64, device=device)             # rewards, dones since the last log line
-    history, t0, last = [], time.perf_counter(), 0
+    stats = RolloutStats(env)                                               # :252-274, on the device
+    history, t0 = [], time.perf_counter()
     for i_step in range(update_steps, steps + 1, update_steps):
         out = env.policy_rollout(learner.params, state, update_steps, check=False)              # :207-227, fused
         res = learner.update(state, out)                                                         # :229-245, fused
         state = out['state']
-        totals += torch.stack([out['rewards'].sum(dtype=torch.float64), out['dones'].sum(dtype=torch.float64)])
+        stats.update(out)
         if i_step % log_interval < update_steps or i_step + update_steps > steps:
-            s = totals.cpu().tolist()
-            totals.zero_()
-            n = (i_step - last) * num_envs
-            dt, last = time.perf_counter() - t0, i_step
+            dt = time.perf_counter() - t0
             loss = res['value_loss'] + res['policy_loss'] - entropy * res['entropy']             # :239-242
-            row = dict(step=i_step, env_steps_per_s=i_step * num_envs / dt, reward_rate=s[0] / n, done_rate=s[1] / n,
-                       loss=float(loss))
+            row = dict(step=i_step, env_steps_per_s=i_step * num_envs / dt, loss=float(loss))
+            # since the last line (the episode columns are left out of a line before which no episode ended)
+            row.update((k, v) for k, v in stats.read().items() if v == v)
             history.append(row)
             if verbose:
                 print(' '.join(f'{k}={v:.4g}' for k, v in row.items()))

@@ -736,6 +736,42 @@ int wurm_a2c_ff_pop_update_gae(float *params, const float *obs0, const float *ob
                                float *exp_avg, float *exp_avg_sq, float *grad_norm, int64_t step, float beta1,
                                float beta2, float eps, float max_grad_norm, void *stream, float *returns_out);
 
+/* ------------------------------------------------------------------------------------------- rollout statistics
+ * The log columns of experiments/main.py:252-316 from the (T,N) outputs of a policy rollout, carried from window to
+ * window: two launches, no host synchronisation, no atomics (bit-identical from run to run).  Kernels:
+ * wurm_amd/csrc/rollout_stats.hpp.
+ *   rewards (T,N) fp32;  dones, edge_collision (T,N) bytes;  self_collision (T,N) bytes, nullable (SimpleGridworld: the
+ *   column stays 0);  probs (T,N,4) fp32, 16-byte aligned, nullable (the entropy column stays 0).
+ *   Per step and env: episode_return += reward, episode_length += 1; grown = size + (reward == 1) (single_snake.py:268-271);
+ *   on done the episode's (return, length, grown) join the episode sums and return and length are cleared; size becomes
+ *   initial_size on done and grown otherwise — the length of the snake main.py:273 reads after env.reset(done).
+ *   initial_size = 0 says that the env has no snake (SimpleGridworld): nothing grows, every size stays 0.
+ *   H = - sum_k p_k log(clamp(p_k, eps32, 1 - eps32)) in fp32, the learner's expression.
+ * carry    (3, N) 4-byte words, read and written: row 0 episode_return (fp32), row 1 episode_length (int32), row 2 size
+ *          (int32).  The caller seeds size with the current length of every snake (zeros for SimpleGridworld).
+ * accum    (num_members, 12) doubles, added to: [0] env steps (T M per call), the sums over steps and envs of [1] done
+ *          (= finished episodes), [2] reward, [3] edge_collision, [4] self_collision, [5] size, [6] H, the sums over
+ *          finished episodes of [7] return, [8] length, [9] final size (grown), and the maxima over them of [10] return
+ *          and [11] final size, folded in with fmax: the caller initialises the two to -infinity.
+ * table    nullable, (num_members, T, 6) doubles, written: the batch sums of step t in the order of accum[1..6].
+ * smooth   (num_members, 6) doubles, read and written: ExponentialMovingAverageTracker(alpha) (wurm/utils.py:323-337)
+ *          over the per-step batch MEANS (the table's rows / M) in step order, in double: a NaN entry is "nothing seen
+ *          yet" and takes the first mean; after that s = alpha x + (1 - alpha) s.  The caller initialises it to NaN.
+ * num_members > 1: member m owns the envs [m M, (m + 1) M), M = num_envs / num_members, and row m of accum, table and
+ * smooth; its numbers are bit for bit those of a stand-alone call on contiguous copies of its M columns.
+ * Refused before any HIP call: a null required pointer, num_envs <= 0, num_steps <= 0, num_members <= 0, num_envs %
+ * num_members != 0, alpha outside [0, 1], a workspace that is too small or not 16-byte aligned (WURM_ERR_INVALID_ARG);
+ * more than 65535 members (WURM_ERR_UNSUPPORTED). */
+
+/* Bytes of the caller-owned workspace (0 for arguments the call refuses): 6 T + 5 doubles per workgroup of 256 envs of a
+ * member, and the per-step sums. */
+int64_t wurm_rollout_stats_workspace_bytes(int64_t num_envs, int64_t num_steps, int64_t num_members);
+
+int wurm_rollout_stats(const float *rewards, const uint8_t *dones, const uint8_t *edge_collision,
+                       const uint8_t *self_collision, const float *probs, void *carry, double *accum, double *smooth,
+                       double *table, void *workspace, int64_t workspace_bytes, int64_t num_envs, int64_t num_steps,
+                       int64_t num_members, int initial_size, double alpha, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ SYMBOLS = [
     'wurm_single_policy_rollout_pop', 'wurm_grid_policy_rollout_pop',
     'wurm_a2c_ff_pop_workspace_bytes', 'wurm_a2c_ff_pop_hyper', 'wurm_a2c_ff_pop_grad', 'wurm_a2c_ff_pop_grad_gae',
     'wurm_a2c_ff_pop_apply', 'wurm_a2c_ff_pop_update', 'wurm_a2c_ff_pop_update_gae',
+    'wurm_rollout_stats_workspace_bytes', 'wurm_rollout_stats',
 ]
 
 
@@ -141,7 +142,8 @@ def lib():
     return _lib
 
 
-_CTYPES = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'uint64_t': ctypes.c_uint64, 'float': ctypes.c_float}
+_CTYPES = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'uint64_t': ctypes.c_uint64, 'float': ctypes.c_float,
+           'double': ctypes.c_double}
 
 
 def _declare_prototypes(l):

@@ -202,3 +202,66 @@ def to_device(fx, device):
     out = {k: fx[k].to(device) for k in ('actions', 'rewards', 'dones')}
     out['observations'] = fx['obs'].to(device)
     return agent.to(device), fx['obs0'].to(device), out
+
+
+ENTRY_POINT_STEMS = ('grad', 'grad_gae', 'update', 'update_gae', 'apply')
+
+
+def run_entry_point(stem, given, device, E, T, N, members=0, lrs=(1e-3,)):
+    """One call of wurm_a2c_ff_<stem> (members == 0) or wurm_a2c_ff_pop_<stem> through ctypes, on inputs that depend on
+    the shape only, with the optional outputs values_out, grad_norm and returns_out handed over (`given`: filled with NaN
+    before, asserted written after) or null.  Returns every tensor the call writes whether they are given or not."""
+    import ctypes
+
+    import numpy as np
+
+    from wurm_amd import _lib
+    lib, pop, gae, rows, P = _lib.lib(), members > 0, stem.endswith('_gae'), max(members, 1), num_params(E)
+    gen = torch.Generator().manual_seed(E + T + N)
+    rnd = lambda *shape: torch.rand(shape, generator=gen)
+    t = {'params': (rnd(rows, P) - 0.5) * 0.5, 'grad': rnd(rows, P) - 0.5, 'exp_avg': (rnd(rows, P) - 0.5) * 1e-2,
+         'exp_avg_sq': rnd(rows, P) * 1e-3, 'losses': torch.zeros(rows, 3)}
+    t = {k: v.to(device) for k, v in t.items()}
+    before = {k: v.clone() for k, v in t.items()}
+    obs0, obs, rewards = rnd(N, E).to(device), rnd(T, N, E).to(device), rnd(T, N).to(device)
+    actions, dones = torch.randint(4, (T, N), generator=gen).to(device), (rnd(T, N) < 0.3).to(device)
+    opt = lambda *shape: torch.full(shape, float('nan'), device=device) if given else None
+    values, returns, norm = opt(T, N), opt(T, N), opt(rows)
+    ptr = lambda x: None if x is None else x.data_ptr()
+    if pop:
+        table = np.zeros((members, 4), dtype=np.float64)
+        lam = [float(np.float32(0.99 * 0.95))] * members
+        cols = [(ctypes.c_float * members)(*v) for v in (lrs, [0.99] * members, [0.01] * members, lam)]
+        assert lib.wurm_a2c_ff_pop_hyper(*[ctypes.addressof(c) for c in cols], members, table.ctypes.data) == _lib.OK
+        hyper = torch.from_numpy(table).to(device)
+        nbytes = lib.wurm_a2c_ff_pop_workspace_bytes(N, T, E, members)
+        hyp, lr, mem, lam_tail = (ptr(hyper),), (), (members,), ()
+    else:
+        nbytes = lib.wurm_a2c_ff_workspace_bytes(N, T, E)
+        hyp, lr, mem, lam_tail = (0.99, 0.01), (lrs[0],), (), (float(np.float32(0.99 * 0.95)),)
+    assert nbytes > 0
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    stream = _lib.stream_ptr(ws.device.index)
+    head = (ptr(t['params']), ptr(obs0), ptr(obs), ptr(actions), ptr(rewards), ptr(dones), *hyp, 0, ptr(t['grad']),
+            ptr(t['losses']), ptr(values), ptr(ws), nbytes, N, T, E, *mem)
+    state = (ptr(t['exp_avg']), ptr(t['exp_avg_sq']), ptr(norm))
+    adam = (3, *lr, 0.9, 0.999, 1e-8, 0.5)
+    tail = (*lam_tail, ptr(returns)) if gae else ()
+    fn = getattr(lib, 'wurm_a2c_ff_' + ('pop_' if pop else '') + stem)
+    if stem == 'apply':
+        rc = fn(ptr(t['params']), ptr(t['grad']), *state, *(hyp if pop else ()), *adam, P, *mem, stream)
+    elif stem.startswith('grad'):
+        rc = fn(*head, stream, *tail)
+    else:
+        rc = fn(*head, *state, *adam, stream, *tail)
+    torch.cuda.synchronize()
+    assert rc == _lib.OK
+    written = ('grad', 'losses') if stem.startswith('grad') else ('params', 'exp_avg', 'exp_avg_sq') if stem == 'apply' \
+        else tuple(t)
+    for k in t:  # the call did its work, and nothing else
+        assert torch.equal(t[k], before[k]) == (k not in written), k
+    if given:
+        assert stem == 'apply' or bool(torch.isfinite(values).all())
+        assert stem.startswith('grad') or bool(torch.isfinite(norm).all())
+        assert not gae or bool(torch.isfinite(returns).all())
+    return t

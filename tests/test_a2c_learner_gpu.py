@@ -159,6 +159,15 @@ def test_clip_and_adam(P, step, kind):
     assert float(((new0.double() - theta.double()) - e64).abs().max() / lr) <= bound(float((e32 - e64).abs().max() / lr))
 
 
+@pytest.mark.parametrize('stem', ref.ENTRY_POINT_STEMS)
+def test_optional_outputs_may_be_null(stem):
+    """values_out, grad_norm and returns_out are optional in the C ABI and FusedA2CLearner always hands them over: every
+    launching entry point once without and once with them, on the same inputs, writes the same bits everywhere else."""
+    without, given = (ref.run_entry_point(stem, g, DEV, E=4, T=2, N=3) for g in (False, True))
+    for k in ('grad', 'losses', 'params', 'exp_avg', 'exp_avg_sq'):
+        assert torch.equal(without[k], given[k]), k
+
+
 # ------------------------------------------------------------------------------------------------ composition
 
 def test_update_is_grad_then_apply():

@@ -6,6 +6,7 @@ import copy
 import pytest
 import torch
 
+from tests import a2c_learner_ref as ref
 from wurm_amd import _lib
 from wurm_amd.agents import FeedforwardAgent
 from wurm_amd.rl import FusedA2CLearner, FusedA2CPopulation
@@ -133,6 +134,17 @@ def test_grad_then_apply_is_update_in_three_launches(use_gae):
     assert torch.equal(one.exp_avg_sq, two.exp_avg_sq)
     assert torch.equal(res['grad'], grad) and torch.equal(res['grad_norm'], norm)
     assert all(torch.equal(res[k], losses[k]) for k in losses)
+
+
+@pytest.mark.parametrize('stem', ref.ENTRY_POINT_STEMS)
+def test_optional_outputs_may_be_null(stem):
+    """values_out, grad_norm and returns_out are optional in the C ABI and FusedA2CPopulation always hands them over:
+    every launching population entry point once without and once with them (P = 3, M = 2, two learning rates), on the
+    same inputs, writes the same bits everywhere else."""
+    without, given = (ref.run_entry_point(stem, g, DEV, E=4, T=2, N=6, members=3, lrs=(1e-3, 3e-4, 1e-3))
+                      for g in (False, True))
+    for k in ('grad', 'losses', 'params', 'exp_avg', 'exp_avg_sq'):
+        assert torch.equal(without[k], given[k]), k
 
 
 def test_agents_show_the_updated_weights():

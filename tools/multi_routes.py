@@ -10,9 +10,13 @@
            that take a lane row (its own functions: oracle parity and the route's name are asserted), then launches on both
            sides of every switch from one wave per workgroup to four, a per-call step and a rollout at 10 x 10, and a
            SimpleGridworld rollout of 6 144 envs.  Compared with --pattern lane_.
-  compare  two such kernel traces, row by row over the library's kernels whose name contains --pattern (default
-           wurm::multi_; the backend's torch copies and fills are dropped by name): kernel name, grid size, workgroup size,
-           LDS size.  Exit status 1 on a difference.
+  learner  the same for the fused A2C learner: `grad`, `apply` and `update` of FusedA2CLearner at (N, T, E) = (1, 1, 4),
+           (300, 5, 75), (65, 20, 507) and of FusedA2CPopulation at (P, M) = (1, 5), (3, 2), (2, 300) (T = 5, E = 75), each
+           with n-step and with GAE returns: N on both sides of the 256 workgroups of the main kernel, the smallest and the
+           largest E.  Compared with --pattern a2c_ff_.
+  compare  two such kernel traces, row by row in order of Start_Timestamp over the library's kernels whose name contains
+           --pattern (default wurm::multi_; the backend's torch copies and fills are dropped by name): kernel name, grid
+           size (x, and y / z where they are not 1), workgroup size, LDS size.  Exit status 1 on a difference.
                python3 tools/multi_routes.py compare [--pattern P] BASE_kernel_trace.csv HEAD_kernel_trace.csv > profiles/rNN_multi_routes.txt"""
 import argparse
 import csv
@@ -103,35 +107,69 @@ def run_lanes(root):
     print('gridworld step', 6144, cases._route(), flush=True)
 
 
+def run_learner(root):
+    sys.path.insert(0, os.path.abspath(root))
+    import torch
+    from wurm_amd import _lib
+    from wurm_amd.agents import FeedforwardAgent
+    from wurm_amd.rl import FusedA2CLearner, FusedA2CPopulation
+    dev, lib = 'cuda:0', _lib.lib()
+
+    def agent(E):
+        return FeedforwardAgent(num_actions=4, num_layers=2, hidden_units=64, num_inputs=E).to(dev)
+
+    def issue(what, learner, N, T, E):
+        g = torch.Generator().manual_seed(N + T + E)
+        state = torch.rand((N, E), generator=g).to(dev)
+        out = dict(observations=torch.rand((T, N, E), generator=g).to(dev), actions=torch.randint(4, (T, N), generator=g).to(dev),
+                   rewards=torch.rand((T, N), generator=g).to(dev), dones=(torch.rand((T, N), generator=g) < 0.2).to(dev))
+        n0 = lib.wurm_launch_count()
+        grad, _ = learner.grad(state, out)
+        learner.apply(grad)
+        learner.update(state, out)
+        torch.cuda.synchronize()
+        print(f'{what:44s} launches {lib.wurm_launch_count() - n0}  step {learner.step}', flush=True)
+
+    for gae in (dict(), dict(use_gae=True, gae_lambda=0.95)):
+        for N, T, E in ((1, 1, 4), (300, 5, 75), (65, 20, 507)):
+            issue(f'learner N={N} T={T} E={E} gae={bool(gae)}', FusedA2CLearner(agent(E), **gae), N, T, E)
+        for P, M in ((1, 5), (3, 2), (2, 300)):
+            pop = FusedA2CPopulation([agent(75) for _ in range(P)], lr=[1e-3 * (1 + p) for p in range(P)], **gae)
+            issue(f'population P={P} M={M} T=5 E=75 gae={bool(gae)}', pop, P * M, 5, 75)
+
+
 def rows(path, pattern):
     out = []
     with open(path) as f:
-        for r in csv.DictReader(f):
+        for r in sorted(csv.DictReader(f), key=lambda r: int(r['Start_Timestamp'])):  # (the file is not in order of dispatch)
             if pattern in r['Kernel_Name']:
+                grid = [int(r['Grid_Size_' + d]) for d in 'XYZ']
+                while len(grid) > 1 and grid[-1] == 1:
+                    grid.pop()
                 out.append((re.sub(r'\(wurm::\w+\)', '', r['Kernel_Name'].replace('void ', '')).replace('wurm::', ''),
-                            int(r['Grid_Size_X']), int(r['Workgroup_Size_X']), int(r['LDS_Block_Size'])))
+                            'x'.join(map(str, grid)), int(r['Workgroup_Size_X']), int(r['LDS_Block_Size'])))
     return out
 
 
 def compare(base, head, pattern):
     b, h = rows(base, pattern), rows(head, pattern)
     print(f'# kernels named *{pattern}* of two rocprofv3 --kernel-trace runs of tools/multi_routes.py, in order of dispatch: {len(b)} / {len(h)} rows')
-    print(f'# {"#":>3s} {"same":4s} {"grid":>6s} {"wg":>4s} {"lds":>7s}  kernel (base; head beside it where it differs)')
+    print(f'# {"#":>3s} {"same":4s} {"grid":>9s} {"wg":>4s} {"lds":>7s}  kernel (base; head beside it where it differs)')
     bad = len(b) != len(h)
     for i in range(max(len(b), len(h))):
         x, y = b[i] if i < len(b) else None, h[i] if i < len(h) else None
         bad |= x != y
         k, g, w, l = x or y
-        print(f'{i:5d} {"yes" if x == y else "NO":4s} {g:6d} {w:4d} {l:7d}  {k}' + ('' if x == y else f'   |   head: {y}'))
+        print(f'{i:5d} {"yes" if x == y else "NO":4s} {g:>9s} {w:4d} {l:7d}  {k}' + ('' if x == y else f'   |   head: {y}'))
     print(f'# {"every row equal" if not bad else "DIFFERENT"}')
     return int(bad)
 
 
 if __name__ == '__main__':
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('what', choices=['run', 'lanes', 'compare'])
+    ap.add_argument('what', choices=['run', 'lanes', 'learner', 'compare'])
     ap.add_argument('traces', nargs='*')
     ap.add_argument('--root', default=HERE)
     ap.add_argument('--pattern', default='wurm::multi_', help='compare: the rows whose kernel name contains this')
     a = ap.parse_intermixed_args()
-    sys.exit(run(a.root) if a.what == 'run' else run_lanes(a.root) if a.what == 'lanes' else compare(*a.traces, a.pattern))
+    sys.exit(compare(*a.traces, a.pattern) if a.what == 'compare' else {'run': run, 'lanes': run_lanes, 'learner': run_learner}[a.what](a.root))

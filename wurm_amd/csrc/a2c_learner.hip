@@ -42,149 +42,141 @@ double as_written(float x)
     return (double)x;
 }
 
-int check_grad_args(const float *params, const float *obs0, const float *obs, const int64_t *actions,
-                    const float *rewards, const uint8_t *dones, int value_loss_kind, float *grad, float *losses,
-                    void *workspace, int64_t workspace_bytes_given, int64_t N, int64_t T, int E)
-{
-    if (!params || !obs0 || !obs || !actions || !rewards || !dones || !grad || !losses || !workspace)
-        return WURM_ERR_INVALID_ARG;
-    if (N <= 0 || T <= 0 || E <= 0 || workspace_bytes_given < 0) return WURM_ERR_INVALID_ARG;
-    if ((uintptr_t)workspace % 16 != 0) return WURM_ERR_INVALID_ARG; // 16-byte accesses
-    if (!supported_inputs(E)) return WURM_ERR_UNSUPPORTED;
-    if (value_loss_kind != WURM_A2C_SMOOTH_L1 && value_loss_kind != WURM_A2C_MSE) return WURM_ERR_UNSUPPORTED;
-    if (workspace_bytes_given < workspace_bytes(N, T, E)) return WURM_ERR_INVALID_ARG;
-    return WURM_OK;
-}
-
-int check_apply_args(const float *params, const float *grad, const float *exp_avg, const float *exp_avg_sq,
-                     int64_t step, float lr, float beta1, float beta2, float eps, int64_t P)
-{
-    if (!params || !grad || !exp_avg || !exp_avg_sq) return WURM_ERR_INVALID_ARG;
-    if (step < 1 || P <= 0) return WURM_ERR_INVALID_ARG;
-    if (!(lr >= 0.0f) || !(beta1 >= 0.0f && beta1 < 1.0f) || !(beta2 >= 0.0f && beta2 < 1.0f) || !(eps >= 0.0f))
-        return WURM_ERR_INVALID_ARG;
-    return WURM_OK;
-}
-
 // gamma * lambda as the caller rounded it: finite and not negative (refused like the other arguments, before any launch)
 bool valid_gamma_lambda(float gamma_lambda) { return std::isfinite(gamma_lambda) && gamma_lambda >= 0.0f; }
 
-template <bool GAE>
-void launch_grad(const float *params, const float *obs0, const float *obs, const int64_t *actions,
-                 const float *rewards, const uint8_t *dones, float gamma, float entropy_coef, int value_loss_kind,
-                 float *grad, float *losses, float *values_out, void *workspace, int64_t N, int64_t T, int E,
-                 hipStream_t stream, float gamma_lambda = 0.0f, float *returns_out = nullptr)
+// What an entry point asks for, as its caller handed it over.  pop: the population kernels, `members` sets of weights of
+// N / members consecutive envs each, gamma, entropy_coef and gamma_lambda out of `hyper`; else the stand-alone kernels,
+// which take the three by value.
+struct GradRequest {
+    const float *params, *obs0, *obs;
+    const int64_t *actions;
+    const float *rewards;
+    const uint8_t *dones;
+    int value_loss_kind;
+    float *grad, *losses, *values_out; // values_out: nullable
+    void *workspace;
+    int64_t workspace_bytes, N, T;
+    int E;
+    bool pop;
+    int64_t members;
+    const double *hyper;
+    float gamma, entropy_coef;
+    bool gae;
+    float gamma_lambda;
+    float *returns_out; // nullable
+};
+
+struct ApplyRequest {
+    float *params;
+    const float *grad;
+    float *exp_avg, *exp_avg_sq, *grad_norm; // grad_norm: nullable
+    int64_t step;
+    float beta1, beta2, eps, max_grad_norm;
+    int64_t num_params;
+    bool pop;
+    int64_t members;
+    const double *hyper;
+    float lr; // stand-alone only: a member's is in its row of `hyper`
+};
+
+int check_grad(const GradRequest &r)
 {
-    typename main_args<GAE>::type a;
-    a.params = params;
-    a.obs0 = obs0;
-    a.obs = obs;
-    a.actions = (const long long *)actions;
-    a.rewards = rewards;
-    a.dones = dones;
-    a.values_out = values_out;
-    a.partials = (float *)workspace;
-    a.G = num_groups(N);
-    a.rows = a.partials + a.G * partial_stride(E);
-    a.N = N;
-    a.T = T;
-    a.E = E;
-    a.loss_kind = value_loss_kind;
-    a.gamma = gamma;
-    a.entropy_coef = entropy_coef;
-    a.inv_B = 1.0f / (float)(N * T);
-    if constexpr (GAE) {
-        a.gamma_lambda = gamma_lambda;
-        a.returns_out = returns_out;
-    }
-    WURM_LAUNCH(a2c_ff_main_kernel<GAE>, dim3((unsigned)a.G), dim3(THREADS), 0, stream, a);
-    const long long P = num_params(E);
-    WURM_LAUNCH(a2c_ff_reduce_kernel, dim3((unsigned)((P + 3 + THREADS - 1) / THREADS)), dim3(THREADS), 0, stream,
-                a.partials, a.G, E, a.inv_B, grad, losses);
+    if (r.gae && !r.pop && !valid_gamma_lambda(r.gamma_lambda)) return WURM_ERR_INVALID_ARG; // (a member's: wurm_a2c_ff_pop_hyper)
+    if (r.pop && (!r.hyper || r.members <= 0 || r.N <= 0 || r.N % r.members != 0)) return WURM_ERR_INVALID_ARG;
+    const int64_t M = r.pop ? r.N / r.members : r.N; // the envs of one set of weights
+    if (!r.params || !r.obs0 || !r.obs || !r.actions || !r.rewards || !r.dones || !r.grad || !r.losses || !r.workspace)
+        return WURM_ERR_INVALID_ARG;
+    if (M <= 0 || r.T <= 0 || r.E <= 0 || r.workspace_bytes < 0) return WURM_ERR_INVALID_ARG;
+    if ((uintptr_t)r.workspace % 16 != 0) return WURM_ERR_INVALID_ARG; // 16-byte accesses
+    if (!supported_inputs(r.E)) return WURM_ERR_UNSUPPORTED;
+    if (r.value_loss_kind != WURM_A2C_SMOOTH_L1 && r.value_loss_kind != WURM_A2C_MSE) return WURM_ERR_UNSUPPORTED;
+    if (r.workspace_bytes < workspace_bytes(M, r.T, r.E)) return WURM_ERR_INVALID_ARG;
+    if (!r.pop) return WURM_OK;
+    if (r.members > 65535) return WURM_ERR_UNSUPPORTED; // the member is the grid's y
+    return r.workspace_bytes < r.members * workspace_bytes(M, r.T, r.E) ? WURM_ERR_INVALID_ARG : WURM_OK;
 }
 
-void launch_apply(float *params, const float *grad, float *exp_avg, float *exp_avg_sq, float *grad_norm, int64_t step,
-                  float lr, float beta1, float beta2, float eps, float max_grad_norm, int64_t P, hipStream_t stream)
+int check_apply(const ApplyRequest &r)
 {
-    const double b1 = as_written(beta1), b2 = as_written(beta2);
-    const float step_size = (float)(as_written(lr) / (1.0 - std::pow(b1, (double)step)));
-    const float bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, (double)step));
-    WURM_LAUNCH(a2c_ff_apply_kernel, dim3((unsigned)((P + APPLY_PER_BLOCK - 1) / APPLY_PER_BLOCK)), dim3(THREADS), 0,
-                stream, params, grad, exp_avg, exp_avg_sq, grad_norm, step_size, bc2_sqrt, (float)b2,
-                (float)(1.0 - b1), (float)(1.0 - b2), (float)as_written(eps), max_grad_norm, (long long)P);
+    if (r.pop && (!r.hyper || r.members <= 0)) return WURM_ERR_INVALID_ARG;
+    if (!r.params || !r.grad || !r.exp_avg || !r.exp_avg_sq) return WURM_ERR_INVALID_ARG;
+    if (r.step < 1 || r.num_params <= 0) return WURM_ERR_INVALID_ARG;
+    if ((!r.pop && !(r.lr >= 0.0f)) || !(r.beta1 >= 0.0f && r.beta1 < 1.0f) || !(r.beta2 >= 0.0f && r.beta2 < 1.0f) ||
+        !(r.eps >= 0.0f))
+        return WURM_ERR_INVALID_ARG; // (a member's lr: wurm_a2c_ff_pop_hyper)
+    return r.pop && r.members > 65535 ? WURM_ERR_UNSUPPORTED : WURM_OK;
 }
 
-// ---- population: P members of M = N / P consecutive envs each (a2c_learner.hpp: a2c_ff_*_pop_kernel)
-
-int check_pop_grad_args(const float *params, const float *obs0, const float *obs, const int64_t *actions,
-                        const float *rewards, const uint8_t *dones, const double *hyper, int value_loss_kind,
-                        float *grad, float *losses, void *workspace, int64_t workspace_bytes_given, int64_t N, int64_t T,
-                        int E, int64_t members)
+// The population's workspace holds every member's partials (member-major), then every member's parked rows: each part is
+// what a stand-alone update of M envs has, `members` times over.
+template <bool GAE, bool POP> void launch_grad(const GradRequest &r, hipStream_t stream)
 {
-    if (!hyper || members <= 0 || N <= 0 || N % members != 0) return WURM_ERR_INVALID_ARG;
-    const int rc = check_grad_args(params, obs0, obs, actions, rewards, dones, value_loss_kind, grad, losses, workspace,
-                                   workspace_bytes_given, N / members, T, E);
-    if (rc != WURM_OK) return rc;
-    if (members > 65535) return WURM_ERR_UNSUPPORTED; // the member is the grid's y
-    if (workspace_bytes_given < members * workspace_bytes(N / members, T, E)) return WURM_ERR_INVALID_ARG;
-    return WURM_OK;
-}
-
-int check_pop_apply_args(const float *params, const float *grad, const float *exp_avg, const float *exp_avg_sq,
-                         const double *hyper, int64_t step, float beta1, float beta2, float eps, int64_t P,
-                         int64_t members)
-{
-    if (!hyper || members <= 0) return WURM_ERR_INVALID_ARG;
-    const int rc = check_apply_args(params, grad, exp_avg, exp_avg_sq, step, 0.0f, beta1, beta2, eps, P);
-    if (rc != WURM_OK) return rc;
-    return members > 65535 ? WURM_ERR_UNSUPPORTED : WURM_OK;
-}
-
-// the workspace holds every member's partials (member-major), then every member's parked rows: each part is what a
-// stand-alone update of M envs has, P times over
-template <bool GAE>
-void launch_pop_grad(const float *params, const float *obs0, const float *obs, const int64_t *actions,
-                     const float *rewards, const uint8_t *dones, const double *hyper, int value_loss_kind, float *grad,
-                     float *losses, float *values_out, void *workspace, int64_t N, int64_t T, int E, int64_t members,
-                     hipStream_t stream, float *returns_out = nullptr)
-{
-    const int64_t M = N / members;
-    typename kernel_args<GAE, true>::type a = {};
-    a.params = params;
-    a.obs0 = obs0;
-    a.obs = obs;
-    a.actions = (const long long *)actions;
-    a.rewards = rewards;
-    a.dones = dones;
-    a.values_out = values_out;
-    a.partials = (float *)workspace;
+    const int64_t sets = POP ? r.members : 1, M = r.N / sets;
+    typename kernel_args<GAE, POP>::type a = {};
+    a.params = r.params;
+    a.obs0 = r.obs0;
+    a.obs = r.obs;
+    a.actions = (const long long *)r.actions;
+    a.rewards = r.rewards;
+    a.dones = r.dones;
+    a.values_out = r.values_out;
+    a.partials = (float *)r.workspace;
     a.G = num_groups(M);
-    a.rows = a.partials + members * a.G * partial_stride(E);
-    a.N = N;
-    a.M = M;
-    a.T = T;
-    a.E = E;
-    a.loss_kind = value_loss_kind;
-    a.inv_B = 1.0f / (float)(M * T);
-    if constexpr (GAE) a.returns_out = returns_out;
-    a.hyper = hyper;
-    WURM_LAUNCH((a2c_ff_main_kernel<GAE, true>), dim3((unsigned)a.G, (unsigned)members), dim3(THREADS), 0, stream, a);
-    const long long P = num_params(E);
-    WURM_LAUNCH(a2c_ff_reduce_pop_kernel, dim3((unsigned)((P + 3 + THREADS - 1) / THREADS), (unsigned)members),
-                dim3(THREADS), 0, stream, a.partials, a.G, E, a.inv_B, grad, losses);
+    a.rows = a.partials + sets * a.G * partial_stride(r.E);
+    a.N = r.N;
+    a.T = r.T;
+    a.E = r.E;
+    a.loss_kind = r.value_loss_kind;
+    a.inv_B = 1.0f / (float)(M * r.T);
+    if constexpr (GAE) a.returns_out = r.returns_out;
+    if constexpr (POP) {
+        a.M = M;
+        a.hyper = r.hyper;
+    } else {
+        a.gamma = r.gamma;
+        a.entropy_coef = r.entropy_coef;
+        if constexpr (GAE) a.gamma_lambda = r.gamma_lambda;
+    }
+    WURM_LAUNCH((a2c_ff_main_kernel<GAE, POP>), dim3((unsigned)a.G, (unsigned)sets), dim3(THREADS), 0, stream, a);
+    const long long P = num_params(r.E);
+    WURM_LAUNCH(POP ? a2c_ff_reduce_pop_kernel : a2c_ff_reduce_kernel,
+                dim3((unsigned)((P + 3 + THREADS - 1) / THREADS), (unsigned)sets), dim3(THREADS), 0, stream, a.partials, a.G,
+                r.E, a.inv_B, r.grad, r.losses);
 }
 
-void launch_pop_apply(float *params, const float *grad, float *exp_avg, float *exp_avg_sq, float *grad_norm,
-                      const double *hyper, int64_t step, float beta1, float beta2, float eps, float max_grad_norm,
-                      int64_t P, int64_t members, hipStream_t stream)
+// step_size = lr / (1 - beta1^step), divided in double and rounded once: here for the stand-alone kernel, by the
+// population kernel itself from bc1 and the member's lr
+void launch_apply(const ApplyRequest &r, hipStream_t stream)
 {
-    const double b1 = as_written(beta1), b2 = as_written(beta2);
-    const double bc1 = 1.0 - std::pow(b1, (double)step); // (launch_apply divides lr by this; here the kernel does)
-    const float bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, (double)step));
-    WURM_LAUNCH(a2c_ff_apply_pop_kernel,
-                dim3((unsigned)((P + APPLY_PER_BLOCK - 1) / APPLY_PER_BLOCK), (unsigned)members), dim3(THREADS), 0,
-                stream, params, grad, exp_avg, exp_avg_sq, grad_norm, hyper, bc1, bc2_sqrt, (float)b2,
-                (float)(1.0 - b1), (float)(1.0 - b2), (float)as_written(eps), max_grad_norm, (long long)P);
+    const double b1 = as_written(r.beta1), b2 = as_written(r.beta2);
+    const double bc1 = 1.0 - std::pow(b1, (double)r.step);
+    const float bc2_sqrt = (float)std::sqrt(1.0 - std::pow(b2, (double)r.step));
+    const float w1 = (float)(1.0 - b1), w2 = (float)(1.0 - b2), eps = (float)as_written(r.eps);
+    const dim3 grid((unsigned)((r.num_params + APPLY_PER_BLOCK - 1) / APPLY_PER_BLOCK), r.pop ? (unsigned)r.members : 1u);
+    if (r.pop)
+        WURM_LAUNCH(a2c_ff_apply_pop_kernel, grid, dim3(THREADS), 0, stream, r.params, r.grad, r.exp_avg, r.exp_avg_sq,
+                    r.grad_norm, r.hyper, bc1, bc2_sqrt, (float)b2, w1, w2, eps, r.max_grad_norm, (long long)r.num_params);
+    else
+        WURM_LAUNCH(a2c_ff_apply_kernel, grid, dim3(THREADS), 0, stream, r.params, r.grad, r.exp_avg, r.exp_avg_sq,
+                    r.grad_norm, (float)(as_written(r.lr) / bc1), bc2_sqrt, (float)b2, w1, w2, eps, r.max_grad_norm,
+                    (long long)r.num_params);
+}
+
+// grad (g), apply (a) or update (both): every check of the grad half, then every check of the apply half, then the launches
+int run(const GradRequest *g, const ApplyRequest *a, void *stream)
+{
+    int rc = g ? check_grad(*g) : WURM_OK;
+    if (rc == WURM_OK && a) rc = check_apply(*a);
+    if (rc != WURM_OK) return rc;
+    (void)hipGetLastError();
+    if (g) {
+        auto *launch = g->pop ? (g->gae ? launch_grad<true, true> : launch_grad<false, true>)
+                              : (g->gae ? launch_grad<true, false> : launch_grad<false, false>);
+        launch(*g, (hipStream_t)stream);
+    }
+    if (a) launch_apply(*a, (hipStream_t)stream);
+    return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
 }
 
 } // namespace
@@ -202,13 +194,9 @@ int wurm_a2c_ff_grad(const float *params, const float *obs0, const float *obs, c
                      float *grad, float *losses, float *values_out, void *workspace, int64_t workspace_bytes,
                      int64_t num_envs, int64_t num_steps, int num_inputs, void *stream)
 {
-    const int rc = check_grad_args(params, obs0, obs, actions, rewards, dones, value_loss_kind, grad, losses, workspace,
-                                   workspace_bytes, num_envs, num_steps, num_inputs);
-    if (rc != WURM_OK) return rc;
-    (void)hipGetLastError();
-    launch_grad<false>(params, obs0, obs, actions, rewards, dones, gamma, entropy_coef, value_loss_kind, grad, losses,
-                       values_out, workspace, num_envs, num_steps, num_inputs, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+    const GradRequest g = {params, obs0, obs, actions, rewards, dones, value_loss_kind, grad, losses, values_out, workspace,
+                           workspace_bytes, num_envs, num_steps, num_inputs, false, 0, nullptr, gamma, entropy_coef};
+    return run(&g, nullptr, stream);
 }
 
 int wurm_a2c_ff_grad_gae(const float *params, const float *obs0, const float *obs, const int64_t *actions,
@@ -217,27 +205,19 @@ int wurm_a2c_ff_grad_gae(const float *params, const float *obs0, const float *ob
                          int64_t workspace_bytes, int64_t num_envs, int64_t num_steps, int num_inputs, void *stream,
                          float gamma_lambda, float *returns_out)
 {
-    if (!valid_gamma_lambda(gamma_lambda)) return WURM_ERR_INVALID_ARG;
-    const int rc = check_grad_args(params, obs0, obs, actions, rewards, dones, value_loss_kind, grad, losses, workspace,
-                                   workspace_bytes, num_envs, num_steps, num_inputs);
-    if (rc != WURM_OK) return rc;
-    (void)hipGetLastError();
-    launch_grad<true>(params, obs0, obs, actions, rewards, dones, gamma, entropy_coef, value_loss_kind, grad, losses,
-                      values_out, workspace, num_envs, num_steps, num_inputs, (hipStream_t)stream, gamma_lambda,
-                      returns_out);
-    return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+    const GradRequest g = {params, obs0, obs, actions, rewards, dones, value_loss_kind, grad, losses, values_out, workspace,
+                           workspace_bytes, num_envs, num_steps, num_inputs, false, 0, nullptr, gamma, entropy_coef,
+                           true, gamma_lambda, returns_out};
+    return run(&g, nullptr, stream);
 }
 
 int wurm_a2c_ff_apply(float *params, const float *grad, float *exp_avg, float *exp_avg_sq, float *grad_norm,
                       int64_t step, float lr, float beta1, float beta2, float eps, float max_grad_norm,
                       int64_t num_params, void *stream)
 {
-    const int rc = check_apply_args(params, grad, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, num_params);
-    if (rc != WURM_OK) return rc;
-    (void)hipGetLastError();
-    launch_apply(params, grad, exp_avg, exp_avg_sq, grad_norm, step, lr, beta1, beta2, eps, max_grad_norm, num_params,
-                 (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+    const ApplyRequest a = {params, grad, exp_avg, exp_avg_sq, grad_norm, step, beta1, beta2, eps, max_grad_norm,
+                            num_params, false, 0, nullptr, lr};
+    return run(nullptr, &a, stream);
 }
 
 int wurm_a2c_ff_hyper_parameter(float x, double *value)
@@ -254,18 +234,11 @@ int wurm_a2c_ff_update(float *params, const float *obs0, const float *obs, const
                        float *exp_avg_sq, float *grad_norm, int64_t step, float lr, float beta1, float beta2, float eps,
                        float max_grad_norm, void *stream)
 {
-    int rc = check_grad_args(params, obs0, obs, actions, rewards, dones, value_loss_kind, grad, losses, workspace,
-                             workspace_bytes, num_envs, num_steps, num_inputs);
-    if (rc != WURM_OK) return rc;
-    const int64_t P = a2c::num_params(num_inputs);
-    rc = check_apply_args(params, grad, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, P);
-    if (rc != WURM_OK) return rc;
-    (void)hipGetLastError();
-    launch_grad<false>(params, obs0, obs, actions, rewards, dones, gamma, entropy_coef, value_loss_kind, grad, losses,
-                       values_out, workspace, num_envs, num_steps, num_inputs, (hipStream_t)stream);
-    launch_apply(params, grad, exp_avg, exp_avg_sq, grad_norm, step, lr, beta1, beta2, eps, max_grad_norm, P,
-                 (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+    const GradRequest g = {params, obs0, obs, actions, rewards, dones, value_loss_kind, grad, losses, values_out, workspace,
+                           workspace_bytes, num_envs, num_steps, num_inputs, false, 0, nullptr, gamma, entropy_coef};
+    const ApplyRequest a = {params, grad, exp_avg, exp_avg_sq, grad_norm, step, beta1, beta2, eps, max_grad_norm,
+                            a2c::num_params(num_inputs), false, 0, nullptr, lr};
+    return run(&g, &a, stream);
 }
 
 int wurm_a2c_ff_update_gae(float *params, const float *obs0, const float *obs, const int64_t *actions,
@@ -276,20 +249,12 @@ int wurm_a2c_ff_update_gae(float *params, const float *obs0, const float *obs, c
                            float beta2, float eps, float max_grad_norm, void *stream, float gamma_lambda,
                            float *returns_out)
 {
-    if (!valid_gamma_lambda(gamma_lambda)) return WURM_ERR_INVALID_ARG;
-    int rc = check_grad_args(params, obs0, obs, actions, rewards, dones, value_loss_kind, grad, losses, workspace,
-                             workspace_bytes, num_envs, num_steps, num_inputs);
-    if (rc != WURM_OK) return rc;
-    const int64_t P = a2c::num_params(num_inputs);
-    rc = check_apply_args(params, grad, exp_avg, exp_avg_sq, step, lr, beta1, beta2, eps, P);
-    if (rc != WURM_OK) return rc;
-    (void)hipGetLastError();
-    launch_grad<true>(params, obs0, obs, actions, rewards, dones, gamma, entropy_coef, value_loss_kind, grad, losses,
-                      values_out, workspace, num_envs, num_steps, num_inputs, (hipStream_t)stream, gamma_lambda,
-                      returns_out);
-    launch_apply(params, grad, exp_avg, exp_avg_sq, grad_norm, step, lr, beta1, beta2, eps, max_grad_norm, P,
-                 (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+    const GradRequest g = {params, obs0, obs, actions, rewards, dones, value_loss_kind, grad, losses, values_out, workspace,
+                           workspace_bytes, num_envs, num_steps, num_inputs, false, 0, nullptr, gamma, entropy_coef,
+                           true, gamma_lambda, returns_out};
+    const ApplyRequest a = {params, grad, exp_avg, exp_avg_sq, grad_norm, step, beta1, beta2, eps, max_grad_norm,
+                            a2c::num_params(num_inputs), false, 0, nullptr, lr};
+    return run(&g, &a, stream);
 }
 
 int64_t wurm_a2c_ff_pop_workspace_bytes(int64_t num_envs, int64_t num_steps, int num_inputs, int64_t num_members)
@@ -305,7 +270,7 @@ int wurm_a2c_ff_pop_hyper(const float *lr, const float *gamma, const float *entr
 {
     if (!lr || !gamma || !entropy_coef || !table || num_members <= 0) return WURM_ERR_INVALID_ARG;
     for (int64_t m = 0; m < num_members; ++m) {
-        if (!(lr[m] >= 0.0f)) return WURM_ERR_INVALID_ARG; // (what check_apply_args asks of a stand-alone lr)
+        if (!(lr[m] >= 0.0f)) return WURM_ERR_INVALID_ARG; // (what check_apply asks of a stand-alone lr)
         if (gamma_lambda && !valid_gamma_lambda(gamma_lambda[m])) return WURM_ERR_INVALID_ARG;
     }
     for (int64_t m = 0; m < num_members; ++m) {
@@ -323,13 +288,9 @@ int wurm_a2c_ff_pop_grad(const float *params, const float *obs0, const float *ob
                          float *grad, float *losses, float *values_out, void *workspace, int64_t workspace_bytes,
                          int64_t num_envs, int64_t num_steps, int num_inputs, int64_t num_members, void *stream)
 {
-    const int rc = check_pop_grad_args(params, obs0, obs, actions, rewards, dones, hyper, value_loss_kind, grad, losses,
-                                       workspace, workspace_bytes, num_envs, num_steps, num_inputs, num_members);
-    if (rc != WURM_OK) return rc;
-    (void)hipGetLastError();
-    launch_pop_grad<false>(params, obs0, obs, actions, rewards, dones, hyper, value_loss_kind, grad, losses, values_out,
-                           workspace, num_envs, num_steps, num_inputs, num_members, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+    const GradRequest g = {params, obs0, obs, actions, rewards, dones, value_loss_kind, grad, losses, values_out, workspace,
+                           workspace_bytes, num_envs, num_steps, num_inputs, true, num_members, hyper};
+    return run(&g, nullptr, stream);
 }
 
 int wurm_a2c_ff_pop_grad_gae(const float *params, const float *obs0, const float *obs, const int64_t *actions,
@@ -338,26 +299,19 @@ int wurm_a2c_ff_pop_grad_gae(const float *params, const float *obs0, const float
                              int64_t num_envs, int64_t num_steps, int num_inputs, int64_t num_members, void *stream,
                              float *returns_out)
 {
-    const int rc = check_pop_grad_args(params, obs0, obs, actions, rewards, dones, hyper, value_loss_kind, grad, losses,
-                                       workspace, workspace_bytes, num_envs, num_steps, num_inputs, num_members);
-    if (rc != WURM_OK) return rc;
-    (void)hipGetLastError();
-    launch_pop_grad<true>(params, obs0, obs, actions, rewards, dones, hyper, value_loss_kind, grad, losses, values_out,
-                          workspace, num_envs, num_steps, num_inputs, num_members, (hipStream_t)stream, returns_out);
-    return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+    const GradRequest g = {params, obs0, obs, actions, rewards, dones, value_loss_kind, grad, losses, values_out, workspace,
+                           workspace_bytes, num_envs, num_steps, num_inputs, true, num_members, hyper, 0.0f, 0.0f,
+                           true, 0.0f, returns_out};
+    return run(&g, nullptr, stream);
 }
 
 int wurm_a2c_ff_pop_apply(float *params, const float *grad, float *exp_avg, float *exp_avg_sq, float *grad_norm,
                           const double *hyper, int64_t step, float beta1, float beta2, float eps, float max_grad_norm,
                           int64_t num_params, int64_t num_members, void *stream)
 {
-    const int rc = check_pop_apply_args(params, grad, exp_avg, exp_avg_sq, hyper, step, beta1, beta2, eps, num_params,
-                                        num_members);
-    if (rc != WURM_OK) return rc;
-    (void)hipGetLastError();
-    launch_pop_apply(params, grad, exp_avg, exp_avg_sq, grad_norm, hyper, step, beta1, beta2, eps, max_grad_norm,
-                     num_params, num_members, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+    const ApplyRequest a = {params, grad, exp_avg, exp_avg_sq, grad_norm, step, beta1, beta2, eps, max_grad_norm,
+                            num_params, true, num_members, hyper};
+    return run(nullptr, &a, stream);
 }
 
 int wurm_a2c_ff_pop_update(float *params, const float *obs0, const float *obs, const int64_t *actions,
@@ -367,18 +321,11 @@ int wurm_a2c_ff_pop_update(float *params, const float *obs0, const float *obs, c
                            float *exp_avg_sq, float *grad_norm, int64_t step, float beta1, float beta2, float eps,
                            float max_grad_norm, void *stream)
 {
-    int rc = check_pop_grad_args(params, obs0, obs, actions, rewards, dones, hyper, value_loss_kind, grad, losses,
-                                 workspace, workspace_bytes, num_envs, num_steps, num_inputs, num_members);
-    if (rc != WURM_OK) return rc;
-    const int64_t P = a2c::num_params(num_inputs);
-    rc = check_pop_apply_args(params, grad, exp_avg, exp_avg_sq, hyper, step, beta1, beta2, eps, P, num_members);
-    if (rc != WURM_OK) return rc;
-    (void)hipGetLastError();
-    launch_pop_grad<false>(params, obs0, obs, actions, rewards, dones, hyper, value_loss_kind, grad, losses, values_out,
-                           workspace, num_envs, num_steps, num_inputs, num_members, (hipStream_t)stream);
-    launch_pop_apply(params, grad, exp_avg, exp_avg_sq, grad_norm, hyper, step, beta1, beta2, eps, max_grad_norm, P,
-                     num_members, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+    const GradRequest g = {params, obs0, obs, actions, rewards, dones, value_loss_kind, grad, losses, values_out, workspace,
+                           workspace_bytes, num_envs, num_steps, num_inputs, true, num_members, hyper};
+    const ApplyRequest a = {params, grad, exp_avg, exp_avg_sq, grad_norm, step, beta1, beta2, eps, max_grad_norm,
+                            a2c::num_params(num_inputs), true, num_members, hyper};
+    return run(&g, &a, stream);
 }
 
 int wurm_a2c_ff_pop_update_gae(float *params, const float *obs0, const float *obs, const int64_t *actions,
@@ -388,18 +335,12 @@ int wurm_a2c_ff_pop_update_gae(float *params, const float *obs0, const float *ob
                                float *exp_avg, float *exp_avg_sq, float *grad_norm, int64_t step, float beta1,
                                float beta2, float eps, float max_grad_norm, void *stream, float *returns_out)
 {
-    int rc = check_pop_grad_args(params, obs0, obs, actions, rewards, dones, hyper, value_loss_kind, grad, losses,
-                                 workspace, workspace_bytes, num_envs, num_steps, num_inputs, num_members);
-    if (rc != WURM_OK) return rc;
-    const int64_t P = a2c::num_params(num_inputs);
-    rc = check_pop_apply_args(params, grad, exp_avg, exp_avg_sq, hyper, step, beta1, beta2, eps, P, num_members);
-    if (rc != WURM_OK) return rc;
-    (void)hipGetLastError();
-    launch_pop_grad<true>(params, obs0, obs, actions, rewards, dones, hyper, value_loss_kind, grad, losses, values_out,
-                          workspace, num_envs, num_steps, num_inputs, num_members, (hipStream_t)stream, returns_out);
-    launch_pop_apply(params, grad, exp_avg, exp_avg_sq, grad_norm, hyper, step, beta1, beta2, eps, max_grad_norm, P,
-                     num_members, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? WURM_OK : WURM_ERR_HIP;
+    const GradRequest g = {params, obs0, obs, actions, rewards, dones, value_loss_kind, grad, losses, values_out, workspace,
+                           workspace_bytes, num_envs, num_steps, num_inputs, true, num_members, hyper, 0.0f, 0.0f,
+                           true, 0.0f, returns_out};
+    const ApplyRequest a = {params, grad, exp_avg, exp_avg_sq, grad_norm, step, beta1, beta2, eps, max_grad_norm,
+                            a2c::num_params(num_inputs), true, num_members, hyper};
+    return run(&g, &a, stream);
 }
 
 } // extern "C"

@@ -13,8 +13,6 @@ custom value loss are not part of the fused path (NotImplementedError: keep wurm
 normalised returns need the mean and the standard deviation of all N T returns between the scan and the backward pass,
 which one workgroup per block of envs cannot know.
 """
-import ctypes
-
 import numpy as np
 import torch
 
@@ -30,45 +28,40 @@ def _parts(agent):
             agent.value_head.weight, agent.value_head.bias]
 
 
-class FusedA2CLearner(object):
-    """A2C loss, backward pass, clip_grad_norm_ and Adam of the 2 x 64 feed-forward actor-critic in HIP.
+class _FusedA2C(object):
+    """What FusedA2CLearner and FusedA2CPopulation (fused_population.py) share: the constructor's refusals, the packing of
+    the agents into one buffer, the checks of a rollout window, the output tensors and the marshalling of the three calls.
+    A subclass says which entry points it calls (`_ENTRY`), how its hyper-parameters are kept (`_own`) and cross the ABI
+    (`_loss_args`, `_step_args`, `_gae_args`), and what one agent's part of `losses` and `grad_norm` is."""
+    _ENTRY = None       # 'wurm_a2c_ff_' or 'wurm_a2c_ff_pop_'
+    _WHOSE = None       # 'agent' / 'agents', for the messages
+    _LOSS_INDEX = None  # the three indices into `losses` that give value_loss, policy_loss and entropy
 
-    Args:
-        agent: a `FeedforwardAgent` that `pack_policy_params` accepts (2 layers, 64 units, 4 actions)
-        lr, betas, eps: torch.optim.Adam's (no weight decay, no amsgrad)
-        gamma: discount;  entropy_coef: weight of the mean entropy;  max_grad_norm: clip_grad_norm_'s (<= 0: none)
-        value_loss: 'smooth_l1' (F.smooth_l1_loss, the reference's default) or 'mse'
-        use_gae, gae_lambda: A2C's; `gae_lambda` is required with `use_gae` and ignored without it
-    """
-
-    def __init__(self, agent: FeedforwardAgent, lr: float = 1e-3, gamma: float = 0.99, entropy_coef: float = 0.0,
-                 max_grad_norm: float = 0.5, betas=(0.9, 0.999), eps: float = 1e-8, value_loss: str = 'smooth_l1',
-                 use_gae: bool = False, normalise_returns: bool = False, gae_lambda: float = None):
-        if normalise_returns:
-            raise NotImplementedError('the fused learner does not normalise returns: use wurm_amd.rl.A2C for that')
+    def __init__(self, agents, lr, gamma, entropy_coef, max_grad_norm, betas, eps, value_loss, use_gae, gae_lambda):
+        name, P = type(self).__name__, len(agents)
         if use_gae and gae_lambda is None:
-            raise NotImplementedError('use_gae=True needs gae_lambda: pass FusedA2CLearner(..., gae_lambda=0.95)')
+            raise NotImplementedError(f'use_gae=True needs gae_lambda: pass {name}(..., gae_lambda=0.95)')
         if value_loss not in VALUE_LOSSES:
             raise NotImplementedError(f"value_loss {value_loss!r}: the fused learner has 'smooth_l1' and 'mse'")
-        flat = pack_policy_params(agent)  # raises NotImplementedError for any other architecture
-        self.agent = agent
-        self.params = flat
-        offset = 0
-        for p in _parts(agent):  # the module's parameters become views of the one buffer
-            n = p.numel()
-            p.data = flat[offset:offset + n].view(p.shape)
-            offset += n
-        self.num_inputs = agent.feedforward[0][0].in_features
-        self.lr, self.gamma, self.entropy_coef, self.max_grad_norm = float(lr), float(gamma), float(entropy_coef), float(max_grad_norm)
+        self.lr, self.gamma = self._own('lr', lr, P), self._own('gamma', gamma, P)
+        self.entropy_coef = self._own('entropy_coef', entropy_coef, P)
+        self.gae_lambda = self._own('gae_lambda', gae_lambda, P) if use_gae else None
+        rows = [pack_policy_params(a) for a in agents]  # raises NotImplementedError for any other architecture
+        self.params = self._buffer(rows)                # (num_params,) or (P, num_params)
+        for row, agent in zip(self.params.view(P, -1), agents):  # every module's parameters become views of its row
+            offset = 0
+            for p in _parts(agent):
+                n = p.numel()
+                p.data = row[offset:offset + n].view(p.shape)
+                offset += n
+        self.num_inputs = agents[0].feedforward[0][0].in_features
+        self.max_grad_norm = float(max_grad_norm)
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         self.value_loss = VALUE_LOSSES[value_loss]
         self.use_gae = bool(use_gae)
-        self.gae_lambda = float(gae_lambda) if use_gae else None
-        # gamma * lambda is one Python float in the reference (a2c.py:56), rounded once: as wurm_amd.rl.a2c_returns does
-        self.gamma_lambda = float(np.float32(self.gamma * self.gae_lambda)) if use_gae else 0.0
         self.step = 0
-        self.exp_avg = torch.zeros_like(flat)
-        self.exp_avg_sq = torch.zeros_like(flat)
+        self.exp_avg = torch.zeros_like(self.params)
+        self.exp_avg_sq = torch.zeros_like(self.params)
         self._workspace = {}
 
     # ------------------------------------------------------------------ plumbing
@@ -76,15 +69,17 @@ class FusedA2CLearner(object):
     def _inputs(self, state, out):
         dev, E = self.params.device, self.num_inputs
         if dev.type != 'cuda':
-            raise _lib.WurmHipError('FusedA2CLearner.grad / update run on the GPU: move the agent to the device first')
+            raise _lib.WurmHipError(f'{type(self).__name__}.grad / update run on the GPU: move the {self._WHOSE} to the '
+                                    f'device first')
         obs, actions, rewards, dones = out['observations'], out['actions'], out['rewards'], out['dones']
         if rewards.dim() != 2 or rewards.numel() == 0:
             raise RuntimeError('rewards must be a non-empty (num_steps, num_envs) tensor')
         T, N = rewards.shape
+        self._check_envs(N)
         for name, t in (('state', state), ('observations', obs), ('actions', actions), ('rewards', rewards),
                         ('dones', dones)):
             if t.device != dev:
-                raise RuntimeError(f'{name} must be on the device of the agent ({dev})')
+                raise RuntimeError(f'{name} must be on the device of the {self._WHOSE} ({dev})')
         if state.numel() != N * E or obs.numel() != T * N * E or state.dtype != torch.float32 or \
                 obs.dtype != torch.float32:
             raise RuntimeError(f'state / observations must be fp32 with {E} inputs per env ({N} envs, {T} steps)')
@@ -94,89 +89,150 @@ class FusedA2CLearner(object):
             raise RuntimeError('rewards must be fp32')
         if dones.shape != (T, N) or dones.dtype not in (torch.bool, torch.uint8):
             raise RuntimeError('dones must be a (num_steps, num_envs) bool tensor')
-        if _parts(self.agent)[0].data_ptr() != self.params.data_ptr():
-            raise RuntimeError('the agent was moved after the learner was built: its parameters left the buffer')
+        if self._moved():
+            raise RuntimeError(f'an agent was moved after the {type(self).__name__} was built: its parameters left the '
+                               f'buffer')
         key = (N, T, E)
         ws = self._workspace.get(key)
         if ws is None:
-            nbytes = _lib.lib().wurm_a2c_ff_workspace_bytes(N, T, E)
+            nbytes = self._workspace_bytes(N, T, E)
             ws = self._workspace[key] = (torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes)
         return (state.contiguous(), obs.contiguous(), actions.contiguous(), rewards.contiguous(), dones.contiguous(),
                 ws, N, T)
 
+    def _check_envs(self, N):
+        pass
+
     def _outputs(self, N, T):
         dev = self.params.device
-        return (torch.empty_like(self.params), torch.empty(3, dtype=torch.float32, device=dev),
+        return (torch.empty_like(self.params), torch.empty(self._losses_shape, dtype=torch.float32, device=dev),
                 torch.empty((T, N), dtype=torch.float32, device=dev),
                 torch.empty((T, N), dtype=torch.float32, device=dev) if self.use_gae else None)
 
-    @staticmethod
-    def _losses(losses, values, returns):
-        res = {'value_loss': losses[0], 'policy_loss': losses[1], 'entropy': losses[2], 'values': values}
+    def _losses(self, losses, values, returns):
+        i = self._LOSS_INDEX
+        res = {'value_loss': losses[i[0]], 'policy_loss': losses[i[1]], 'entropy': losses[i[2]], 'values': values}
         if returns is not None:
             res['returns'] = returns
         return res
 
-    def _gae_args(self, returns):
-        return (ctypes.c_float(self.gamma_lambda), _lib.ptr(returns)) if self.use_gae else ()
+    def _grad_args(self, x0, obs, actions, rewards, dones, grad, losses, values, ws, nbytes, N, T):
+        """the arguments `grad` and `update` share, up to num_inputs / num_members"""
+        ptr = _lib.ptr
+        return (ptr(self.params), ptr(x0), ptr(obs), ptr(actions), ptr(rewards), ptr(dones), *self._loss_args(),
+                self.value_loss, ptr(grad), ptr(losses), ptr(values), ptr(ws), nbytes, N, T, self.num_inputs,
+                *self._members)
 
-    # ------------------------------------------------------------------ the two calls
+    def _adam_args(self, norm, apply=False):
+        """the optimiser state and what follows it, up to max_grad_norm"""
+        return (_lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(norm), *self._step_args(apply), self.betas[0],
+                self.betas[1], self.eps, self.max_grad_norm)
+
+    # ------------------------------------------------------------------ the calls
 
     def grad(self, state: torch.Tensor, out: dict):
-        """(flat_grad, losses): the unclipped gradient of the loss in `pack_policy_params` order and a dict of 0-dim
-        device tensors `value_loss`, `policy_loss`, `entropy` (+ `values`, (T, N): the value of every policy input; with
-        GAE also `returns`, (T, N)).
-        state: the observation the rollout started from; out: what `policy_rollout` returned (or any dict with
-        `observations` (T,N,...), `actions`, `rewards`, `dones` (T,N))."""
+        """(grad, losses): the unclipped gradient(s) of the loss, of the shape of `params` in `pack_policy_params` order,
+        and a dict of device tensors `value_loss`, `policy_loss`, `entropy` — 0-dim for FusedA2CLearner, (P,) for
+        FusedA2CPopulation — plus `values`, (T, N): the value of every policy input, and with GAE `returns`, (T, N).
+        state: the observation the rollout started from, (N, ...); out: what `policy_rollout` returned (or any dict
+        with `observations` (T, N, ...), `actions`, `rewards`, `dones` (T, N))."""
         x0, obs, actions, rewards, dones, (ws, nbytes), N, T = self._inputs(state, out)
         grad, losses, values, returns = self._outputs(N, T)
         dev = self.params.device
-        fn = _lib.lib().wurm_a2c_ff_grad_gae if self.use_gae else _lib.lib().wurm_a2c_ff_grad
-        rc = _lib.call(dev.index, fn, _lib.ptr(self.params), _lib.ptr(x0), _lib.ptr(obs),
-                       _lib.ptr(actions), _lib.ptr(rewards), _lib.ptr(dones), ctypes.c_float(self.gamma),
-                       ctypes.c_float(self.entropy_coef), self.value_loss, _lib.ptr(grad), _lib.ptr(losses),
-                       _lib.ptr(values), _lib.ptr(ws), _lib.i64(nbytes), _lib.i64(N), _lib.i64(T), self.num_inputs,
+        fn = getattr(_lib.lib(), self._ENTRY + ('grad_gae' if self.use_gae else 'grad'))
+        rc = _lib.call(dev.index, fn, *self._grad_args(x0, obs, actions, rewards, dones, grad, losses, values, ws, nbytes,
+                                                       N, T),
                        _lib.stream_ptr(dev.index), *self._gae_args(returns))
-        _lib.check(rc, 'FusedA2CLearner.grad')
+        _lib.check(rc, f'{type(self).__name__}.grad')
         return grad, self._losses(losses, values, returns)
 
     def apply(self, grad: torch.Tensor) -> torch.Tensor:
-        """clip_grad_norm_ + one Adam step on a flat gradient (not modified); returns its norm (0-dim device tensor)."""
+        """clip_grad_norm_ + one Adam step of every agent on a gradient of the shape of `params` (not modified); returns
+        its norm (device tensor: 0-dim for FusedA2CLearner, (P,) for FusedA2CPopulation)."""
         dev = self.params.device
         if dev.type != 'cuda':
-            raise _lib.WurmHipError('FusedA2CLearner.apply runs on the GPU')
-        if grad.device != dev or grad.dtype != torch.float32 or grad.numel() != self.params.numel() or \
-                not grad.is_contiguous():
-            raise RuntimeError('grad must be a contiguous fp32 device tensor with one element per parameter')
-        norm = torch.empty(1, dtype=torch.float32, device=dev)
-        rc = _lib.call(dev.index, _lib.lib().wurm_a2c_ff_apply, _lib.ptr(self.params), _lib.ptr(grad),
-                       _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(norm), _lib.i64(self.step + 1),
-                       ctypes.c_float(self.lr), ctypes.c_float(self.betas[0]), ctypes.c_float(self.betas[1]),
-                       ctypes.c_float(self.eps), ctypes.c_float(self.max_grad_norm), _lib.i64(self.params.numel()),
-                       _lib.stream_ptr(dev.index))
-        _lib.check(rc, 'FusedA2CLearner.apply')
+            raise _lib.WurmHipError(f'{type(self).__name__}.apply runs on the GPU')
+        if grad.device != dev or grad.dtype != torch.float32 or not self._fits(grad) or not grad.is_contiguous():
+            raise RuntimeError(f'grad must be a contiguous fp32 device tensor that matches params '
+                               f'{tuple(self.params.shape)}')
+        norm = torch.empty(self._norm_shape, dtype=torch.float32, device=dev)
+        args = self._adam_args(norm, apply=True)
+        rc = _lib.call(dev.index, getattr(_lib.lib(), self._ENTRY + 'apply'), _lib.ptr(self.params), _lib.ptr(grad),
+                       *args, self.params.shape[-1], *self._members, _lib.stream_ptr(dev.index))
+        _lib.check(rc, f'{type(self).__name__}.apply')
         self.step += 1
-        return norm[0]
+        return self._per_agent(norm)
 
     def update(self, state: torch.Tensor, out: dict) -> dict:
-        """One optimiser step from one rollout window: the losses of `grad` plus `grad_norm` (before clipping) and
-        `grad` (unclipped), all device tensors — nothing is copied to the host."""
+        """One optimiser step of every agent from one rollout window, in three launches: the losses of `grad` plus
+        `grad_norm` (before clipping) and `grad` (unclipped), all device tensors — nothing is copied to the host."""
         x0, obs, actions, rewards, dones, (ws, nbytes), N, T = self._inputs(state, out)
         grad, losses, values, returns = self._outputs(N, T)
         dev = self.params.device
-        norm = torch.empty(1, dtype=torch.float32, device=dev)
-        fn = _lib.lib().wurm_a2c_ff_update_gae if self.use_gae else _lib.lib().wurm_a2c_ff_update
-        rc = _lib.call(dev.index, fn, _lib.ptr(self.params), _lib.ptr(x0), _lib.ptr(obs),
-                       _lib.ptr(actions), _lib.ptr(rewards), _lib.ptr(dones), ctypes.c_float(self.gamma),
-                       ctypes.c_float(self.entropy_coef), self.value_loss, _lib.ptr(grad), _lib.ptr(losses),
-                       _lib.ptr(values), _lib.ptr(ws), _lib.i64(nbytes), _lib.i64(N), _lib.i64(T), self.num_inputs,
-                       _lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(norm), _lib.i64(self.step + 1),
-                       ctypes.c_float(self.lr), ctypes.c_float(self.betas[0]), ctypes.c_float(self.betas[1]),
-                       ctypes.c_float(self.eps), ctypes.c_float(self.max_grad_norm), _lib.stream_ptr(dev.index),
-                       *self._gae_args(returns))
-        _lib.check(rc, 'FusedA2CLearner.update')
+        norm = torch.empty(self._norm_shape, dtype=torch.float32, device=dev)
+        fn = getattr(_lib.lib(), self._ENTRY + ('update_gae' if self.use_gae else 'update'))
+        rc = _lib.call(dev.index, fn, *self._grad_args(x0, obs, actions, rewards, dones, grad, losses, values, ws, nbytes,
+                                                       N, T),
+                       *self._adam_args(norm), _lib.stream_ptr(dev.index), *self._gae_args(returns))
+        _lib.check(rc, f'{type(self).__name__}.update')
         self.step += 1
         res = self._losses(losses, values, returns)
-        res['grad_norm'] = norm[0]
+        res['grad_norm'] = self._per_agent(norm)
         res['grad'] = grad
         return res
+
+
+class FusedA2CLearner(_FusedA2C):
+    """A2C loss, backward pass, clip_grad_norm_ and Adam of the 2 x 64 feed-forward actor-critic in HIP.
+
+    Args:
+        agent: a `FeedforwardAgent` that `pack_policy_params` accepts (2 layers, 64 units, 4 actions)
+        lr, betas, eps: torch.optim.Adam's (no weight decay, no amsgrad)
+        gamma: discount;  entropy_coef: weight of the mean entropy;  max_grad_norm: clip_grad_norm_'s (<= 0: none)
+        value_loss: 'smooth_l1' (F.smooth_l1_loss, the reference's default) or 'mse'
+        use_gae, gae_lambda: A2C's; `gae_lambda` is required with `use_gae` and ignored without it
+    """
+    _ENTRY, _WHOSE, _LOSS_INDEX = 'wurm_a2c_ff_', 'agent', (0, 1, 2)
+    _members, _losses_shape, _norm_shape = (), (3,), (1,)
+
+    def __init__(self, agent: FeedforwardAgent, lr: float = 1e-3, gamma: float = 0.99, entropy_coef: float = 0.0,
+                 max_grad_norm: float = 0.5, betas=(0.9, 0.999), eps: float = 1e-8, value_loss: str = 'smooth_l1',
+                 use_gae: bool = False, normalise_returns: bool = False, gae_lambda: float = None):
+        if normalise_returns:
+            raise NotImplementedError('the fused learner does not normalise returns: use wurm_amd.rl.A2C for that')
+        super().__init__([agent], lr, gamma, entropy_coef, max_grad_norm, betas, eps, value_loss, use_gae, gae_lambda)
+        self.agent = agent
+        # gamma * lambda is one Python float in the reference (a2c.py:56), rounded once: as wurm_amd.rl.a2c_returns does
+        self.gamma_lambda = float(np.float32(self.gamma * self.gae_lambda)) if use_gae else 0.0
+
+    @staticmethod
+    def _own(name, value, P):
+        return float(value)
+
+    @staticmethod
+    def _buffer(rows):
+        return rows[0]
+
+    def _moved(self):
+        return _parts(self.agent)[0].data_ptr() != self.params.data_ptr()
+
+    @staticmethod
+    def _workspace_bytes(N, T, E):
+        return _lib.lib().wurm_a2c_ff_workspace_bytes(N, T, E)
+
+    def _fits(self, grad):
+        return grad.numel() == self.params.numel()
+
+    @staticmethod
+    def _per_agent(norm):
+        return norm[0]
+
+    # the stand-alone entry points take the hyper-parameters by value
+    def _loss_args(self):
+        return self.gamma, self.entropy_coef
+
+    def _step_args(self, apply):
+        return self.step + 1, self.lr
+
+    def _gae_args(self, returns):
+        return (self.gamma_lambda, _lib.ptr(returns)) if self.use_gae else ()

@@ -736,6 +736,29 @@ int wurm_a2c_ff_pop_update_gae(float *params, const float *obs0, const float *ob
                                float *exp_avg, float *exp_avg_sq, float *grad_norm, int64_t step, float beta1,
                                float beta2, float eps, float max_grad_norm, void *stream, float *returns_out);
 
+/* Population-based training, the exploit / explore step, in two launches on `stream` (kernels: wurm_amd/csrc/a2c_pbt.hpp):
+ * no atomics, no grid-wide barrier, nothing read back.
+ *   scores  DEVICE (num_members) doubles, only read; a NaN counts as -infinity.  rank(p) = #{q : score_q > score_p or
+ *           (score_q == score_p and q < p)}: best first, ties to the lower index.
+ *   order   DEVICE (num_members) int32, written: order[rank(p)] = p, the members best to worst.
+ *   parent  DEVICE (num_members) int32, written: p itself for a member of rank < num_members - num_replace, which keeps
+ *           everything; else src = order[mulhi(w0, num_replace)], one of the best num_replace, with w the Philox4x32-10
+ *           block of (seed; env = p, call = generation, purpose 9, sub 0).  Such a member's rows of params, exp_avg and
+ *           exp_avg_sq (num_members, num_params) become copies of row src, and its row of hyper becomes
+ *             lr           = min(max(hyper[src][0] * (w1 >> 31 ? lr_up : lr_down), lr_lo), lr_hi), a double;
+ *             entropy_coef = (double)(float)min(max(hyper[src][2] * (w2 >> 31 ? e_up : e_down), e_lo), e_hi): the
+ *                            table holds it as a float;
+ *             gamma and gamma_lambda: those of src.
+ *   perturb HOST, 8 doubles: lr_down, lr_up, lr_lo, lr_hi, e_down, e_up, e_lo, e_hi; read before the call returns.
+ * No row that is read as a source is written by the same call (sources have rank < num_replace, destinations rank >=
+ * num_members - num_replace).  num_replace = 0 still writes order and parent = identity.  step is shared and untouched.
+ * Refused before any HIP call: a null pointer, num_params <= 0, num_members <= 0, num_replace < 0, 2 num_replace >
+ * num_members, generation < 0, a factor that is not finite or <= 0, bounds with lo < 0, lo > hi or a NaN (hi = +infinity
+ * is allowed) (WURM_ERR_INVALID_ARG); more than 65535 members (WURM_ERR_UNSUPPORTED). */
+int wurm_a2c_ff_pop_exploit(float *params, float *exp_avg, float *exp_avg_sq, double *hyper, const double *scores,
+                            int32_t *order, int32_t *parent, int64_t num_params, int64_t num_members,
+                            int64_t num_replace, const double *perturb, uint64_t seed, int64_t generation, void *stream);
+
 /* ------------------------------------------------------------------------------------------- rollout statistics
  * The log columns of experiments/main.py:252-316 from the (T,N) outputs of a policy rollout, carried from window to
  * window: two launches, no host synchronisation, no atomics (bit-identical from run to run).  Kernels:

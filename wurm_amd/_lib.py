@@ -33,7 +33,7 @@ SYMBOLS = [
     'wurm_a2c_ff_hyper_parameter', 'wurm_a2c_ff_grad_gae', 'wurm_a2c_ff_update_gae',
     'wurm_single_policy_rollout_pop', 'wurm_grid_policy_rollout_pop',
     'wurm_a2c_ff_pop_workspace_bytes', 'wurm_a2c_ff_pop_hyper', 'wurm_a2c_ff_pop_grad', 'wurm_a2c_ff_pop_grad_gae',
-    'wurm_a2c_ff_pop_apply', 'wurm_a2c_ff_pop_update', 'wurm_a2c_ff_pop_update_gae',
+    'wurm_a2c_ff_pop_apply', 'wurm_a2c_ff_pop_update', 'wurm_a2c_ff_pop_update_gae', 'wurm_a2c_ff_pop_exploit',
     'wurm_rollout_stats_workspace_bytes', 'wurm_rollout_stats',
 ]
 

@@ -18,7 +18,8 @@ typedef unsigned int u32;
 
 constexpr int WAVE = 64;
 
-// RNG purposes: one Philox stream per (env, call, purpose, sub-block).  Must match oracle/oracle_common.h.
+// RNG purposes: one Philox stream per (env, call, purpose, sub-block).  0 - 8 must match oracle/oracle_common.h; 9 is
+// library-only (the oracle never draws it): env = member, call = generation (a2c_pbt.hpp).
 enum : u32 {
     RNG_FOOD = 0,
     RNG_RESET = 1,
@@ -28,7 +29,8 @@ enum : u32 {
     RNG_RATE_FOOD = 5,
     RNG_SPAWN = 6,
     RNG_COLOUR = 7,
-    RNG_POLICY = 8
+    RNG_POLICY = 8,
+    RNG_PBT = 9
 };
 
 struct Words {

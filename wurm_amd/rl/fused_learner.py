@@ -181,6 +181,35 @@ class _FusedA2C(object):
         res['grad'] = grad
         return res
 
+    # ------------------------------------------------------------------ checkpoints
+
+    _STATE_TENSORS = ('params', 'exp_avg', 'exp_avg_sq')  # (the population adds its hyper-parameter table)
+    _STATE_NUMBERS = ('step',)                            # (and its generation)
+
+    def state_dict(self) -> dict:
+        """Clones of the weights and the Adam state, plus `step` (FusedA2CPopulation: also the hyper-parameter table
+        `hyper` and `generation`): what `load_state_dict` of a learner built the same way needs to go on bit for bit.
+        The constructor's arguments are not part of it.  Works on CPU tensors too: no kernel is involved."""
+        state = {name: getattr(self, name).clone() for name in self._STATE_TENSORS}
+        state.update((name, getattr(self, name)) for name in self._STATE_NUMBERS)
+        return state
+
+    def load_state_dict(self, state: dict):
+        """Copies a `state_dict()` IN PLACE: the modules' parameters stay views of `params` and show the loaded weights.
+        Every shape and dtype is checked before anything is copied (RuntimeError, nothing changed)."""
+        for name in self._STATE_TENSORS:
+            mine, theirs = getattr(self, name), state[name]
+            if theirs.shape != mine.shape or theirs.dtype != mine.dtype:
+                raise RuntimeError(f'{name}: expected {tuple(mine.shape)} {mine.dtype}, got {tuple(theirs.shape)} '
+                                   f'{theirs.dtype}')
+        numbers = {name: int(state[name]) for name in self._STATE_NUMBERS}
+        if any(v < 0 for v in numbers.values()):
+            raise RuntimeError(f'{self._STATE_NUMBERS} must not be negative, got {numbers}')
+        for name in self._STATE_TENSORS:
+            getattr(self, name).copy_(state[name])
+        for name, value in numbers.items():
+            setattr(self, name, value)
+
 
 class FusedA2CLearner(_FusedA2C):
     """A2C loss, backward pass, clip_grad_norm_ and Adam of the 2 x 64 feed-forward actor-critic in HIP.

@@ -7,8 +7,14 @@ and `exp_avg_sq`, and its own lr, gamma, entropy_coef and gae_lambda.  Every res
 `FusedA2CLearner` of its own computes from contiguous copies of its columns: its part of the grid is the grid of that
 stand-alone update.  The per-member hyper-parameters live in a small device table built once, here; an update copies
 nothing to the device and reads nothing back.
+
+`exploit(scores)` is the step of population-based training: the worst members take over the weights, Adam state and
+hyper-parameters of good ones and perturb the copied lr and entropy_coef, on the device, in two launches
+(wurm_amd/csrc/a2c_pbt.hpp).  From then on the table, not the constructor's arguments, says what the members train with:
+`hyperparameters()` reads it.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -35,11 +41,14 @@ class FusedA2CPopulation(_FusedA2C):
         lr, gamma, entropy_coef, gae_lambda: a scalar, or a sequence of P (one per agent)
         max_grad_norm, betas, eps, value_loss, use_gae: shared, as FusedA2CLearner's
     Return normalisation is not offered (FusedA2CLearner explains why).
+    `lr`, `gamma`, `entropy_coef` and `gae_lambda` remain the values the population was built with; `hyperparameters()`
+    gives the current ones, which `exploit` changes.
     `grad`, `apply` and `update` take and return what FusedA2CLearner's do with a leading member dimension: `grad`
     (P, num_params), the losses and `grad_norm` (P,); state and out are what a `policy_rollout(..., population=P)` started
     from and returned, (N, ...) and (T, N, ...).
     """
     _ENTRY, _WHOSE, _LOSS_INDEX = 'wurm_a2c_ff_pop_', 'agents', tuple((slice(None), i) for i in range(3))
+    _STATE_TENSORS, _STATE_NUMBERS = _FusedA2C._STATE_TENSORS + ('hyper',), _FusedA2C._STATE_NUMBERS + ('generation',)
 
     def __init__(self, agents, lr=1e-3, gamma=0.99, entropy_coef=0.0, max_grad_norm: float = 0.5, betas=(0.9, 0.999),
                  eps: float = 1e-8, value_loss: str = 'smooth_l1', use_gae: bool = False, gae_lambda=None):
@@ -61,6 +70,7 @@ class FusedA2CPopulation(_FusedA2C):
                                               _lib.i64(P), table.ctypes.data)
         _lib.check(rc, 'FusedA2CPopulation: lr / gae_lambda')
         self.hyper = torch.from_numpy(table).to(self.params.device)
+        self.generation = 0  # the number of `exploit` calls so far: the counter of their random draws
 
     _own = staticmethod(_per_member)
 
@@ -98,3 +108,60 @@ class FusedA2CPopulation(_FusedA2C):
 
     def _gae_args(self, returns):
         return (_lib.ptr(returns),) if self.use_gae else ()
+
+    # ------------------------------------------------------------------ population-based training
+
+    def exploit(self, scores: torch.Tensor, num_replace: int = None, fraction: float = 0.25, lr_factors=(0.8, 1.2),
+                entropy_factors=(0.8, 1.2), lr_bounds=(0.0, math.inf), entropy_bounds=(0.0, math.inf),
+                seed: int = 0) -> dict:
+        """The exploit / explore step of population-based training, in two launches with nothing read back
+        (include/wurm_hip.h: wurm_a2c_ff_pop_exploit): each of the worst `num_replace` members by `scores` takes the
+        weights, the Adam state and the hyper-parameters of a member drawn from the best `num_replace`; its copied lr and
+        entropy_coef are each multiplied by one of the two factors (a coin each) and clamped to the bounds.  Everyone
+        else keeps everything.  The agents' modules are views of the rows and show the copied weights; `step` is shared
+        and unchanged.
+
+        scores: (P,) device tensor, higher is better, a NaN is worst — `stats.smooth[:, k]` of a
+            `RolloutStats(env, population=P)`, say.  float64 is used as it is, float32 is converted on the device.
+        num_replace: k, at most P // 2; default int(fraction * P).
+        seed: of the draws, together with `self.generation`, which counts the calls (it starts at 0).
+        Returns {'order': (P,) int32, the members best to worst, 'parent': (P,) int32, whose weights member p now has
+        (p itself unless it was replaced)}, both on the device."""
+        P = self.num_members
+        k = int(fraction * P) if num_replace is None else int(num_replace)
+        if k < 0 or 2 * k > P:
+            raise ValueError(f'num_replace must lie in [0, {P // 2}] for {P} members, got {k}')
+        if scores.shape != (P,) or scores.dtype not in (torch.float64, torch.float32):
+            raise RuntimeError(f'scores must be a ({P},) float64 or float32 tensor, got {tuple(scores.shape)} '
+                               f'{scores.dtype}')
+        dev = self.params.device
+        if dev.type != 'cuda':
+            raise _lib.WurmHipError('FusedA2CPopulation.exploit runs on the GPU: move the agents to the device first')
+        if scores.device != dev:
+            raise RuntimeError(f'scores must be on the device of the agents ({dev})')
+        # (no `_moved()` here: it walks the P agents on the host, which at P = 256 costs a hundred times the two kernels;
+        # the next `update` makes that check and raises)
+        scores = scores.to(torch.float64).contiguous()
+        order = torch.empty(P, dtype=torch.int32, device=dev)
+        parent = torch.empty(P, dtype=torch.int32, device=dev)
+        perturb = (ctypes.c_double * 8)(lr_factors[0], lr_factors[1], lr_bounds[0], lr_bounds[1], entropy_factors[0],
+                                        entropy_factors[1], entropy_bounds[0], entropy_bounds[1])
+        rc = _lib.call(dev.index, _lib.lib().wurm_a2c_ff_pop_exploit, _lib.ptr(self.params), _lib.ptr(self.exp_avg),
+                       _lib.ptr(self.exp_avg_sq), _lib.ptr(self.hyper), _lib.ptr(scores), _lib.ptr(order),
+                       _lib.ptr(parent), _lib.i64(self.params.shape[1]), _lib.i64(P), _lib.i64(k),
+                       ctypes.addressof(perturb), _lib.u64(seed), _lib.i64(self.generation), _lib.stream_ptr(dev.index))
+        _lib.check(rc, 'FusedA2CPopulation.exploit: lr_factors / entropy_factors / lr_bounds / entropy_bounds')
+        self.generation += 1
+        return {'order': order, 'parent': parent}
+
+    def hyperparameters(self) -> dict:
+        """The members' CURRENT hyper-parameters, the one host copy of the table: {'lr', 'gamma', 'entropy_coef'} and,
+        with GAE, 'gae_lambda', each a list of P floats.  The table holds gamma * gae_lambda rounded to float, so
+        'gae_lambda' is that column divided by gamma (0 where gamma is 0): the constructor's value to float rounding.
+        The attributes `lr`, `gamma`, `entropy_coef` and `gae_lambda` stay what the population was BUILT with; after an
+        `exploit` they no longer describe the members, and this does."""
+        lr, gamma, entropy_coef, gamma_lambda = self.hyper.t().cpu().tolist()
+        res = {'lr': lr, 'gamma': gamma, 'entropy_coef': entropy_coef}
+        if self.use_gae:
+            res['gae_lambda'] = [gl / g if g else 0.0 for gl, g in zip(gamma_lambda, gamma)]
+        return res

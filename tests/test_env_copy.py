@@ -51,6 +51,81 @@ def test_multi_snake_copy_and_pickle(monkeypatch, mirror, machine):
             assert a == b and d.final() == d2.final(), (prefix, clone)
 
 
+def _assert_plain(state):
+    """nothing of the machine in what __getstate__ hands out: by type, all the way down the containers"""
+    import ctypes
+    import weakref
+    from wurm_amd.envs import _fast_step, _mirror, _multi_parts
+    machine = [ctypes._SimpleCData, ctypes.Structure, ctypes.Union, ctypes.Array, ctypes._Pointer, ctypes._CFuncPtr,
+               weakref.ReferenceType, _fast_step.PyStepper, _mirror.Mirror, _multi_parts.Masks, _multi_parts.ResetObs,
+               _multi_parts.Outputs, _multi_parts._LazyDict]
+    try:
+        from wurm_amd import _fastcall
+        machine.append(_fastcall.Stepper)
+    except ImportError:
+        pass
+
+    def walk(path, v):
+        assert not isinstance(v, tuple(machine)), (path, type(v))
+        assert not callable(v) or isinstance(v, type), (path, v)        # (a bound method would drag its object along)
+        if isinstance(v, dict):
+            for k, x in v.items():
+                walk(path + (k,), x)
+        elif isinstance(v, (tuple, list, set, frozenset)):
+            for i, x in enumerate(v):
+                walk(path + (i,), x)
+    walk((), state)
+
+
+def _five_more(sim, d, iteration):
+    del sim.calls[:]
+    seen = [iteration(d) for _ in range(5)]
+    return list(sim.calls), seen, d.final()
+
+
+def test_the_state_of_a_multi_snake_holds_nothing_of_the_machine(monkeypatch):
+    """what _make_machine makes stays out of a copy, whatever it comes to make: asserted by type, not by a list of names"""
+    from wurm_amd.envs import multi_snake as ms
+    sim = pe.install_multi(monkeypatch, True, 'python')
+    d = pe.make_multi('lazy')
+    d.step(); d.reset_d_noobs(); d.step()
+    assert d.check() is None and d.env._chk is not None              # the mirror, and the masks asked for
+    d.step(); d.reset_d(); d.step(); d.reset_d()                     # a precomputed reset observation
+    d.step_split()                                                   # K action tensors of their own: stacked
+    d.env._lazy_obs_mode = True
+    d.reset_d_keep()                                                 # a postponed reset, what it returned still held
+    assert type(d.kept) is ms._LazyResetObs and d.kept._env is not None and d.env._pending
+    assert d.env.mirror_state()['state'] == 'lazy'
+    state = d.env.__getstate__()
+    _assert_plain(state)
+    assert d.kept._env is None and not d.env._pending                # (taking the state settled both)
+    d2 = pe.MultiDriver(pickle.loads(pickle.dumps(d.env)), False)
+    d2.k = d.k
+
+    def iteration(x):
+        return x.step(), x.reset_d_noobs(), x.read_rewards()
+    assert _five_more(sim, d, iteration) == _five_more(sim, d2, iteration)
+
+
+@pytest.mark.parametrize('kind', ['single', 'grid'])
+def test_the_state_of_a_single_env_holds_nothing_of_the_machine(monkeypatch, kind):
+    sim = pe.install_single(monkeypatch, kind, 'python')
+    d = pe.make_single(kind, 'lazy' if kind == 'single' else False)
+    d.step(); d.reset_d_noobs(); d.step()
+    if kind == 'single':
+        assert d.check() is None
+    d.step(); d.reset_d(); d.step(); d.reset_d(); d.step()
+    d.reset_d_noobs()                                                # a postponed reset
+    assert d.env._pending
+    _assert_plain(d.env.__getstate__())
+    d2 = type(d)(pickle.loads(pickle.dumps(d.env)), False)
+    d2.k = d.k
+
+    def iteration(x):
+        return x.step(), x.reset_d_noobs(), x.read_done()
+    assert _five_more(sim, d, iteration) == _five_more(sim, d2, iteration)
+
+
 def test_info_of_a_step_pickles_as_a_plain_dict(monkeypatch):
     pe.install_multi(monkeypatch, True, 'python')
     d = pe.make_multi(None)

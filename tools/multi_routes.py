@@ -14,6 +14,9 @@
            (300, 5, 75), (65, 20, 507) and of FusedA2CPopulation at (P, M) = (1, 5), (3, 2), (2, 300) (T = 5, E = 75), each
            with n-step and with GAE returns: N on both sides of the 256 workgroups of the main kernel, the smallest and the
            largest E.  Compared with --pattern a2c_ff_.
+  host     the same for the MultiSnake CLASS (a refactor of its host layer): a per-call and rollout script on a mirrored
+           (40 x 3 x 12, resident_mirror=True) and an unmirrored shape — both reset forms, check_consistency(), a state
+           attribute read and edited, rollouts with and without observations.  Compared with the default pattern.
   compare  two such kernel traces, row by row in order of Start_Timestamp over the library's kernels whose name contains
            --pattern (default wurm::multi_; the backend's torch copies and fills are dropped by name): kernel name, grid
            size (x, and y / z where they are not 1), workgroup size, LDS size.  Exit status 1 on a difference.
@@ -138,6 +141,39 @@ def run_learner(root):
             issue(f'population P={P} M={M} T=5 E=75 gae={bool(gae)}', pop, P * M, 5, 75)
 
 
+def run_host(root):
+    sys.path.insert(0, os.path.abspath(root))
+    import torch
+    from wurm_amd import _lib
+    from wurm_amd.envs import MultiSnake
+    lib, N, K, S = _lib.lib(), 40, 3, 12
+    acts = torch.randint(8, (24, K, N), generator=torch.Generator().manual_seed(3)).cuda()
+    keys = ['agent_%d' % i for i in range(K)]
+    for mirror in (True, False):
+        env = MultiSnake(N, K, S, device='cuda:0', seed=7, resident_mirror=mirror, food_mode='random_rate', respawn_mode='any')
+        n0 = lib.wurm_launch_count()
+        for t in range(12):
+            d = env.step(dict(zip(keys, acts[t])))[2]['__all__']
+            if t < 4:
+                env.reset(d, return_observations=False)
+            else:
+                env.reset(d)
+            if t >= 8:
+                env.check_consistency()
+        b = env.bodies
+        env.step(dict(zip(keys, acts[12])))
+        b[0, 0, 0, 0] = 0.0
+        env.step(dict(zip(keys, acts[13])))
+        del b
+        env.rollout(acts[14:17])
+        env.step(dict(zip(keys, acts[17])))
+        env.rollout(acts[18:21], return_observations=False)
+        env.check_consistency()
+        torch.cuda.synchronize()
+        print(f'MultiSnake {N} x {K} x {S} resident_mirror={mirror}: launches {lib.wurm_launch_count() - n0}  '
+              f'{env.mirror_state()["state"]}', flush=True)
+
+
 def rows(path, pattern):
     out = []
     with open(path) as f:
@@ -167,9 +203,9 @@ def compare(base, head, pattern):
 
 if __name__ == '__main__':
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('what', choices=['run', 'lanes', 'learner', 'compare'])
+    ap.add_argument('what', choices=['run', 'lanes', 'learner', 'host', 'compare'])
     ap.add_argument('traces', nargs='*')
     ap.add_argument('--root', default=HERE)
     ap.add_argument('--pattern', default='wurm::multi_', help='compare: the rows whose kernel name contains this')
     a = ap.parse_intermixed_args()
-    sys.exit(compare(*a.traces, a.pattern) if a.what == 'compare' else {'run': run, 'lanes': run_lanes, 'learner': run_learner}[a.what](a.root))
+    sys.exit(compare(*a.traces, a.pattern) if a.what == 'compare' else {'run': run, 'lanes': run_lanes, 'learner': run_learner, 'host': run_host}[a.what](a.root))

@@ -39,27 +39,14 @@ can do, SingleSnake's other snake lengths, it raises itself), _start_args()
 _configure_call(block), _make_out(i) -> what step returns for slot i.
 """
 import ctypes
-import os
 
 import torch
 
 from wurm_amd import _lib
+from wurm_amd.envs._mirror import Mirror, parse_mirror_policy  # noqa: F401 (parse_mirror_policy: imported from here too)
 
 
 _storage_use_count = torch._C._storage_Use_Count
-
-
-def parse_mirror_policy(value):
-    """`resident_mirror` keyword of the env classes -> None (automatic: by batch size, with the adaptive rules), False
-    (never), 'lazy' (whenever the shape is served, no adaptive rule; True means this) or 'eager' (the same, but every step
-    also writes the state tensors)."""
-    if value is None or value is False:
-        return value
-    if value is True or value == 'lazy':
-        return 'lazy'
-    if value == 'eager':
-        return 'eager'
-    raise ValueError("resident_mirror must be None, True, False, 'lazy' or 'eager'")
 
 
 class PyStepper(object):
@@ -252,8 +239,22 @@ class FastStepMixin(object):
     _RESIDENT_FNS = ('wurm_single_resident_bytes', 'wurm_single_resident_size', 'wurm_single_resident_flush')
     # rollout() of no steps: True = the mirror is not looked at (SingleSnake), False = it is brought in line with the mode first
     _EMPTY_ROLLOUT_SKIPS_MIRROR = False
+    # the texts of mirror_state()['why'] that name the classes' tensor
+    _MIRROR_WORDS = {
+        'written': '`envs`',
+        'touched': 'adaptive: the state was written by something other than the step launch after %d of the last %d steps',
+        'held': 'the caller holds the state tensor: every step writes `envs`, in-place edits are watched',
+        'unwatchable': 'the state tensor has no version counter (inference mode): cannot be watched',
+        'unserved': 'shape / observation mode not served by the mirror kernels, or batch below the threshold',
+        'refused': "refused: the launch that built it found envs outside the lane kernel's domain (hand-made states) — the "
+                   'state tensor is stepped as it is, two launches per call, until something writes the state again'}
+    _mirror = property(lambda self: self._mir.buf)   # (the name tests and tools read)
 
-    def _fast_init(self):
+    def _fast_init(self, envs=None):
+        """Derived state, ALL of it (`envs`: the state tensor of a copy; None: a fresh one).  Whatever this method adds to
+        the object is left out of a copy / pickle and made again by this method on the other side."""
+        d = self.__dict__
+        before = set(d)
         N = self.num_envs
         c = self._c = _lib.SingleCall()
         c.num_envs, c.env_offset, c.seed, c.size = N, self.env_offset, _lib.u64(self.seed), self.size
@@ -265,7 +266,7 @@ class FastStepMixin(object):
         self._get_device = _lib.accessors()[0]
         self._pend = None              # (N) bytes: the kernels' own copy of the last step's `done`
         self._slab_mode = None
-        self._envs = torch.zeros((N, self._CHANNELS, self.size, self.size), device=self.device)
+        self._envs = torch.zeros((N, self._CHANNELS, self.size, self.size), device=self.device) if envs is None else envs
         self._fs.state = (self._envs,)
         self._envs_ok = None           # the state tensor that has been validated (None: validate before the next launch)
         # env.done: what the caller (or the constructor / rollout) assigned, valid until the next step overwrites it
@@ -273,43 +274,35 @@ class FastStepMixin(object):
         # compact mirror of the state the step launch reads instead of `envs` (wurm_single_call.resident; large 9 x 9
         # batches).  The library marks it current after each step launch; everything else that writes the state clears
         # the mark (_touch); a state tensor the caller got hold of is watched for in-place edits through its version counter
-        self._mirror, self._mirror_key, self._mirror_off = None, None, False
-        pol = parse_mirror_policy(getattr(self, '_resident_policy', None))
-        self._resident_policy = pol
-        if pol is False:
-            self._mirror_off = True
-        self._lazy_mirror = pol != 'eager' and os.environ.get('WURM_RESIDENT_LAZY', '1') != '0'
-        self._write_outs = self._touches = self._mirror_step0 = 0
+        # (`fs.watch`: the step machine compares it in front of every launch)
+        self._mir = Mirror(c, ctypes.addressof(c), self._RESIDENT_FNS, getattr(self, '_resident_policy', None),
+                           self._MIRROR_WORDS, False, self.device)
         # check_consistency()'s masks from inside the step launch (wurm_single_call.check_mask): asked for once the caller
         # has called check_consistency(), valid for the state the last step left until anything else touches the state
         self._chk, self._chk_armed_at, self._chk_void_at, self._check_calls, self._check_step = None, 1 << 62, -1, 0, 0
-        self._mirror_why = 'resident_mirror=False' if pol is False else 'no step yet'
         self._stor = None
+        self._v_obs = self._v_reward = self._v_done2 = self._v_selfc = self._v_edgec = None   # rows of the output slab
+        self._fast_made = frozenset(set(d) - before) | {'_fast_made'}
 
     # ------------------------------------------------------------------ copy / pickle
     # The reference's envs are plain attribute bags: copy.deepcopy(env) and pickle work on them (single_snake.py:55-102).
     # Here the object also owns ctypes blocks, a step machine and device buffers that are derived state: they are left out
     # and rebuilt on the other side (`_fast_init`), after the postponed reset and a lazy mirror have been applied to the
     # tensor that IS the state.
-    _DERIVED = ('_c', '_sl', '_fs', '_get_device', '_pend', '_slab_mode', '_envs_ok', '_done', '_done_stamp', '_mirror',
-                '_mirror_key', '_mirror_off', '_lazy_mirror', '_write_outs', '_touches', '_mirror_step0', '_chk',
-                '_chk_armed_at', '_chk_void_at', '_check_calls', '_check_step', '_mirror_why', '_stor', '_v_obs', '_v_reward',
-                '_v_done2', '_v_selfc', '_v_edgec')
-
     def __getstate__(self):
         envs = self._state()   # (applies a postponed reset, writes a lazy mirror out)
-        st = {k: v for k, v in self.__dict__.items() if k not in self._DERIVED}
-        st['_envs'] = envs
+        st = {k: v for k, v in self.__dict__.items() if k not in self._fast_made}
+        st['_copy_envs'] = envs
         st['_copy_call'], st['_copy_done'] = int(self._fs.call), self.done
         return st
 
     def __setstate__(self, st):
         st = dict(st)
-        call, done, envs = st.pop('_copy_call'), st.pop('_copy_done'), st.pop('_envs')
+        call, done, envs = st.pop('_copy_call'), st.pop('_copy_done'), st.pop('_copy_envs')
         self.__dict__.update(st)
-        self._fast_init()
-        self.envs = envs
-        self._fs.watch, self._fs.watch_version = None, -1   # (nobody holds the restored tensor but this object)
+        # (our own tensor object, as the `envs` setter makes one: after copy.copy the two env objects share the state's storage
+        # and `_alias_free` must see the other holder; nobody else holds the restored tensor: not watched)
+        self._fast_init(envs.detach() if isinstance(envs, torch.Tensor) else envs)
         self._fs.call = call
         self.done = done
 
@@ -419,50 +412,23 @@ class FastStepMixin(object):
         """Something other than the step launch is about to look at the state or to write it: a lazy mirror is written
         out to `envs` first (the step launches have not been writing them), and the next step rebuilds the mirror."""
         self._chk_void_at = self._fs.steps  # the masks of the last step's launch no longer describe the state
-        self._write_out()
-        c = self._c
-        if c.resident_valid and c.resident:
-            # a loop in which (nearly) every step is followed by something that writes the state some other way — an eager
-            # reset, a rollout — rebuilds the mirror every step for nothing (SimpleGridworld: with a synchronous read of the
-            # build's verdict each time, and 2 = refused again while a hand-made env stays): switch it off for this env object
-            self._touches += 1
-            if self._resident_policy is None and self._touches >= 8 and \
-                    2 * self._touches >= self._fs.steps - self._mirror_step0:
-                self._mirror_off, self._mirror, self._mirror_key = True, None, None
-                c.resident = None
-                self._mirror_why = ('adaptive: the state was written by something other than the step launch after %d of the '
-                                    'last %d steps' % (self._touches, self._fs.steps - self._mirror_step0))
-        c.resident_valid = 0
+        self._mir.touch(self._fs.steps)
 
     def _write_out(self):
         """`envs` from a lazy mirror (which stays current)"""
-        c = self._c
-        if c.resident_valid == 1 and c.resident and c.resident_lazy:   # (2: SimpleGridworld's mirror refused — the planes are the state)
-            rc = _lib.call(self.device.index, getattr(_lib.lib(), self._RESIDENT_FNS[2]), ctypes.addressof(c),
-                           _lib.stream_ptr(self.device.index))
-            _lib.check(rc, self._RESIDENT_FNS[2])
-            # a caller that keeps looking at the state (check_consistency() every step, experiments/main.py:214-215) pays
-            # a whole-state write per look in the lazy form: from the second one on the steps write `envs` themselves
-            self._write_outs += 1
-            if self._write_outs >= 2 and self._resident_policy is None:
-                c.resident_lazy = 0
-                self._mirror_why = 'adaptive: the state was looked at twice, every step writes `envs` from now on'
+        self._mir.write_out()
 
     def _watch(self, t):
         """The caller holds the state tensor `t` from now on and may edit it in place at any time: every step compares its
         version counter (in-place torch ops bump it) and rebuilds the mirror after a change.  Tensors without version
         counters (made under torch.inference_mode()) cannot be watched: no mirror from then on."""
         fs = self._fs
-        self._c.resident_lazy = 0  # the caller may READ it at any time as well: the step launches write `envs` from now on
-        if self._mirror is not None:
-            self._mirror_why = 'the caller holds the state tensor: every step writes `envs`, in-place edits are watched'
+        self._mir.holds()
         try:
             fs.watch, fs.watch_version = t, t._version
         except (RuntimeError, AttributeError):
             fs.watch, fs.watch_version = None, -1
-            self._mirror_off, self._mirror, self._mirror_key = True, None, None
-            self._c.resident, self._c.resident_valid = None, 0
-            self._mirror_why = 'the state tensor has no version counter (inference mode): cannot be watched'
+            self._mir.unwatchable()
 
     def _mirror_sync(self):
         """the step machine saw another version of the watched state tensor: the mirror is stale"""
@@ -478,46 +444,21 @@ class FastStepMixin(object):
                 self._watch(w)
 
     def _setup_mirror(self, m: int, n: int):
-        key = (m, n)
-        if key == self._mirror_key:
+        if (m, n) == self._mir.key:
             return
         # another observation mode: a LAZY mirror holds steps `envs` has not seen — written out while the old mirror is
         # still the one the call block names, before it is replaced or dropped
         self._touch()
-        self._mirror_key = key
-        nbytes = 0
-        if not self._mirror_off:
-            size_fn = getattr(_lib.lib(), self._RESIDENT_FNS[0 if self._resident_policy is None else 1])
-            args = (m, n) if self._CHANNELS == 3 else (m,)   # (SimpleGridworld's observations have no crop radius)
-            nbytes = int(size_fn(_lib.i64(self.num_envs), self.size, *args))
-            if not self._mirror_off:
-                self._mirror_why = ('shape / observation mode not served by the mirror kernels, or batch below the threshold'
-                                    if nbytes == 0 else 'on')
-        self._mirror = torch.empty(nbytes, dtype=torch.uint8, device=self.device) if nbytes > 0 else None
-        self._touches, self._mirror_step0 = 0, self._fs.steps
-        self._c.resident = self._mirror.data_ptr() if self._mirror is not None else None
-        self._c.resident_valid = 0
-        # lazy (the step launches do not write `envs`, _touch() brings them up to date) as long as the caller has never
-        # got hold of the state tensor
-        self._c.resident_lazy = int(self._mirror is not None and self._fs.watch is None and self._lazy_mirror and
-                                    (self._write_outs < 2 or self._resident_policy is not None))
-        if self._mirror is not None and self._fs.watch is not None:
-            self._mirror_why = 'the caller holds the state tensor: every step writes `envs`, in-place edits are watched'
+        args = (m, n) if self._CHANNELS == 3 else (m,)   # (SimpleGridworld's observations have no crop radius)
+        self._mir.setup((m, n), (_lib.i64(self.num_envs), self.size) + args, self._fs.steps, self._fs.watch is not None,
+                        self.device)
 
     def mirror_state(self) -> dict:
         """What the resident mirror of the state is doing for this env object right now:
         `state` 'off' (every step reads `envs`), 'eager' (steps read the mirror and write `envs`) or 'lazy' (steps do
         not write `envs`; they are written out when something looks at them); `why`; `policy` (the `resident_mirror`
         keyword: None = automatic); `current`: the mirror describes the state (False: the next step rebuilds it)."""
-        c = self._c
-        on = bool(c.resident) and self._mirror is not None
-        why = self._mirror_why
-        if on and c.resident_valid == 2:
-            why = ("refused: the launch that built it found envs outside the lane kernel's domain (hand-made states) — the "
-                   'state tensor is stepped as it is, two launches per call, until something writes the state again')
-        return {'state': 'off' if not on else ('lazy' if c.resident_lazy else 'eager'), 'why': why,
-                'policy': self._resident_policy, 'current': bool(on and c.resident_valid == 1),
-                'bytes': int(self._mirror.numel()) if on else 0}
+        return self._mir.state()
 
     def _step_check_mask(self):
         """(N) int32 masks of wurm_single_check for the state as it is now, computed inside the last step's launch

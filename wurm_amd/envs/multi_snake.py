@@ -30,11 +30,17 @@ Large batches (from 2^20 cells: wurm_multi_resident_bytes) hand the step launch 
 check_consistency()'s masks once the caller has used that method; the tensors stay the state — reading one of the three
 attributes writes them out (and from then on every step writes them), every other entry point goes through `_touch()`,
 tensors the caller holds are watched for in-place edits (DESIGN.md §5, §7 deviation 9).
+
+Where things live.  This class: the reference's API, the deferred-reset glue around the step machine `_fs`
+(envs/_fast_step.py) and the watch on tensors the caller holds (`_watched`).  `_make_machine` makes everything else, and
+whatever it makes is left out of a copy / pickle and made again on the other side: the argument block `_mc` and the slabs
+`_sl` of the launches, `_mir` (envs/_mirror.py: the mirror buffer, the `resident_mirror` policy, the two adaptive rules,
+`mirror_state()` — the controller SingleSnake and SimpleGridworld use too), and from envs/_multi_parts.py `_masks` (the
+in-launch consistency masks and their arming), `_reset_obs` (does the caller keep what `reset` returns) and `_out` (the
+output slab, `rewards` / `boost_this_step`).  `step` and `reset(done)` reach `_fs.step_multi` / `_fs.reset_lazy` without a
+Python-level call in between.
 """
 import ctypes
-import os
-import sys
-import weakref
 from collections import namedtuple, OrderedDict
 from typing import Dict, Optional, Tuple
 
@@ -42,6 +48,9 @@ import torch
 
 from wurm_amd import _lib
 from wurm_amd.constants import DEFAULT_DEVICE, EPS
+from wurm_amd.envs._fast_step import _make_stepper
+from wurm_amd.envs._mirror import Mirror
+from wurm_amd.envs._multi_parts import Masks, Outputs, ResetObs, _LazyInfo, _LazyResetObs  # noqa: F401 (the dict types: API)
 from wurm_amd.envs.single_snake import _draw_seed
 
 Spec = namedtuple('Spec', ['reward_threshold'])
@@ -59,6 +68,30 @@ def _version_of(t: torch.Tensor) -> int:
         return -1
 
 
+def _bind_state(c, tensors):
+    """the six state tensors into the argument block of the per-call launches (and of wurm_multi_resident_flush)"""
+    foods, heads, bodies, dones, orientations, colours = tensors
+    c.foods, c.heads, c.bodies = foods.data_ptr(), heads.data_ptr(), bodies.data_ptr()
+    c.dones, c.orientations, c.colours = dones.data_ptr(), orientations.data_ptr(), colours.data_ptr()
+
+
+def _action_block(vals, N, dev):
+    """(address, tensor or None) of the (K, N) int64 action block of a step: reference :492 stacks in dict order; the kernel
+    reads agent i's action of env e at [i*N + e].  Rows of one (K, N) int64 tensor (e.g. `tape[t, i]`) are used where they
+    lie, anything else is stacked."""
+    a0 = vals[0]
+    a_ptr = a0.data_ptr() if (a0.dtype is torch.long and a0.device == dev) else 0
+    if a_ptr:
+        for i, v in enumerate(vals):
+            if v.dtype is not torch.long or v.dim() != 1 or not v.is_contiguous() or v.data_ptr() != a_ptr + i * 8 * N:
+                a_ptr = 0
+                break
+    if a_ptr:
+        return a_ptr, None
+    block = torch.stack([v.reshape(N) for v in vals]).to(device=dev, dtype=torch.long).contiguous()
+    return block.data_ptr(), block
+
+
 class _Flushing(object):
     """State attribute of MultiSnake: reading or assigning it first applies a postponed reset(done)."""
 
@@ -71,7 +104,7 @@ class _Flushing(object):
         if obj._pending:
             obj._flush()
         obj._obs_after = None  # the caller may edit what it gets: reset(done) then observes again instead of reusing it
-        obj._chk_fresh = False  # ... and the consistency mask the step launch computed no longer describes the state
+        obj._masks.void()      # ... and the consistency mask the step launch computed no longer describes the state
         t = getattr(obj, self.slot)
         if self.slot in _MIRRORED:
             obj._escape(t)     # the caller holds a state tensor from now on (resident mirror: written out, watched)
@@ -88,101 +121,14 @@ class _Flushing(object):
             if old is not None and obj._watched:
                 obj._watched = tuple((x, v) for x, v in obj._watched if x is not old)
         obj._last_fresh = False
-        obj._chk_fresh = False
-        obj._state_dirty = True  # step() re-validates the layout and re-reads the pointers
+        obj._masks.void()
+        obj._fs.ok = False  # the next step goes through _slow_step, which re-validates the layout and re-reads the pointers
         if isinstance(value, torch.Tensor):
             value = value.detach()   # (our own tensor object: see __get__)
         setattr(obj, self.slot, value)
         obj._sync_state()
         if self.slot in _MIRRORED:
             obj._escape(value)
-
-
-class _LazyInfo(dict):
-    """`info` of one step (reference :707-729: snake_collision_i, edge_collision_i, food_i, size_i, boost_i).  A dict whose 5 K
-    tensors are carved from the step's output block the first time anything looks at it: a view object per row is most of
-    what a step costs on the host, and callers that read `info` every step are rare (the reference's loops log from it every
-    few hundred steps).  Every reading method fills it first, so it behaves as the plain dict it then is."""
-    __slots__ = ('_src',)
-
-    def __init__(self, src):
-        dict.__init__(self)
-        self._src = src
-
-    def _fill(self):
-        src = self._src
-        if src is not None:
-            self._src = None
-            f, b, keys, K = src  # the step's packed floats (6K, N) / flags (7K + 1, N): agent-major rows from 3K on
-            rf, rb = f[3 * K:].unbind(0), b[3 * K:7 * K].unbind(0)
-            k_snake, k_edge, k_food, k_boost, k_size = keys
-            dict.update(self, zip(k_snake, rb[2 * K:3 * K]))
-            dict.update(self, zip(k_edge, rb[3 * K:]))
-            dict.update(self, zip(k_food, rf[K:2 * K]))
-            dict.update(self, zip(k_size, rf[2 * K:]))
-            dict.update(self, zip(k_boost, rb[K:2 * K]))
-
-    def __missing__(self, key):
-        if self._src is None:
-            raise KeyError(key)
-        self._fill()
-        return dict.__getitem__(self, key)
-
-    def __reduce__(self):
-        self._fill()
-        return (dict, (dict(self),))
-
-
-def _filling(name):
-    method = getattr(dict, name)
-
-    def wrapper(self, *a, **kw):
-        self._fill()
-        return method(self, *a, **kw)
-    wrapper.__name__ = name
-    return wrapper
-
-
-for _name in ('__contains__', '__iter__', '__len__', '__eq__', '__ne__', '__repr__', '__setitem__', '__delitem__', '__or__',
-              '__ror__', '__ior__', '__reversed__', 'get', 'keys', 'values', 'items', 'copy', 'pop', 'popitem', 'setdefault',
-              'update', 'clear'):
-    setattr(_LazyInfo, _name, _filling(_name))
-
-
-class _LazyResetObs(dict):
-    """What `reset(done)` returns once the caller has been seen to DISCARD it (experiments/speeds.py:30-38 does: `env.reset(
-    done['__all__'])` as a statement): the K observations of the reference's return value (:834-836) are not worth a second
-    observation stream out of every step launch for a caller that drops them.  The dict fills itself — the postponed reset
-    applied, `_observe` of the mode the reset was called in — the first time anything reads it; and if the caller still
-    holds it when the state is about to change (the next step, anything that flushes the postponed reset) the env fills it
-    first, so it always holds what the reference would have returned.  Either way the env goes back to precomputing."""
-    __slots__ = ('_env', '_mode', '__weakref__')
-
-    def __init__(self, env, mode):
-        dict.__init__(self)
-        self._env, self._mode = env, mode
-
-    def _fill(self):
-        env = self._env
-        if env is not None:
-            self._env = None
-            env._settle_reset_obs(self)
-
-    def __missing__(self, key):
-        if self._env is None:
-            raise KeyError(key)
-        self._fill()
-        return dict.__getitem__(self, key)
-
-    def __reduce__(self):
-        self._fill()
-        return (dict, (dict(self),))
-
-
-for _name in ('__contains__', '__iter__', '__len__', '__eq__', '__ne__', '__repr__', '__setitem__', '__delitem__', '__or__',
-              '__ror__', '__ior__', '__reversed__', 'get', 'keys', 'values', 'items', 'copy', 'pop', 'popitem', 'setdefault',
-              'update', 'clear'):
-    setattr(_LazyResetObs, _name, _filling(_name))
 
 
 class _Dynamic(object):
@@ -230,46 +176,17 @@ class MultiSnake(object):
     _obs_after = property(lambda self: self._fs.obs_after, lambda self, v: setattr(self._fs, 'obs_after', v))
     _want_after = property(lambda self: self._fs.want_obs_after, lambda self, v: setattr(self._fs, 'want_obs_after', v))
     _steps = property(lambda self: self._fs.steps)
-    _mirror = None          # the compact mirror of foods / heads / bodies the step launch reads instead of them
-    _mirror_off = False
-    _lazy_mirror = os.environ.get('WURM_RESIDENT_LAZY', '1') != '0'
-    _watched = ()           # (tensor, version) of state tensors the caller holds: in-place edits make the mirror stale
-    _write_outs = _touches = 0
-    _chk = None             # (2, N) int32: check_consistency's masks of the post-step / post-reset state, from the step launch
-    _chk_has_after = False
-    _chk_armed_at, _chk_void_at = 1 << 62, -1
-    _check_calls = _check_step = 0
-    _rewards_t = _boost_t = _mc_mode = _info = _rewards_src = None
-    _rewards_at = _boost_at = 0
-    _slab = None            # (out_f32, out_u8) of the current output slab
-    _mc_ready = False
-    # what reset(done) returned last / whether the caller keeps it (module docstring: "discarded reset observations")
-    _reset_obs_probe = None  # the precomputed dict the last reset(done) handed out: looked at by the next step
-    _reset_obs_drops = 0     # consecutive resets whose returned dict nobody held at the next step
-    _RESET_OBS_DROPS = 3     # ... this many: reset(done) returns a _LazyResetObs and the steps stop precomputing
-    _lazy_obs_mode = False
-    _lazy_obs_ref = None     # weak reference to the _LazyResetObs of the postponed reset, while it may still need filling
-    _abuf = None             # (K, N) int64: the action block of a step whose K action tensors had to be stacked
-
-    @property
-    def _state_dirty(self):
-        return not self._fs.ok
-
-    @_state_dirty.setter
-    def _state_dirty(self, v):
-        if v:
-            self._fs.ok = False  # the next step goes through _slow_step, which re-validates the layout and re-reads the pointers
-
-    @property
-    def _chk_fresh(self):
-        """the masks the last step's launch wrote describe the state as it is (nothing has looked at or written it since)"""
-        c, st = self._mc, self._fs.steps
-        return bool(c.resident) and bool(c.check_mask) and st > self._chk_armed_at and st > self._chk_void_at
-
-    @_chk_fresh.setter
-    def _chk_fresh(self, v):
-        if not v:
-            self._chk_void_at = self._fs.steps
+    # fields of the role objects (wurm_amd/envs/_mirror.py, _multi_parts.py) under the names tests and tools read
+    _mirror = property(lambda self: self._mir.buf)
+    _chk = property(lambda self: self._masks.buf)
+    _lazy_obs_mode = property(lambda self: self._reset_obs.lazy_mode, lambda self, v: setattr(self._reset_obs, 'lazy_mode', v))
+    # the texts of mirror_state()['why'] that name this class's tensors
+    _MIRROR_WORDS = {
+        'written': 'the tensors',
+        'touched': 'adaptive: the state was written by something other than the step launch after %d of %d steps',
+        'held': 'the caller holds a state tensor: every step writes them, in-place edits are watched',
+        'unwatchable': 'a state tensor has no version counter (inference mode): cannot be watched',
+        'unserved': 'batch below the threshold (2^20 cells), or shape not served'}
 
     foods = _Flushing('foods')
     heads = _Flushing('heads')
@@ -323,20 +240,13 @@ class MultiSnake(object):
         `resident_mirror` — None: large batches step on a compact mirror of foods / heads / bodies chosen
         by batch size with adaptive rules; False: never; True / 'lazy' / 'eager': always, without the adaptive rules
         (`env.mirror_state()` tells what is in effect and why)."""
-        from wurm_amd.envs._fast_step import parse_mirror_policy
         self.device = _lib.require_device(device)
-        self._make_machine(num_envs, num_snakes)
-        self._resident_policy = pol = parse_mirror_policy(resident_mirror)
-        self._mirror_off = pol is False
-        self._lazy_mirror = pol != 'eager' and MultiSnake._lazy_mirror
-        self._mirror_why = 'resident_mirror=False' if pol is False else 'no step yet'
         self.num_envs = num_envs
         self.num_snakes = num_snakes
-        self.lazy_reset = bool(lazy_reset)
-        self._pend = None            # (N) bytes: the kernels' own copy of the last step's dones['__all__']
-        self._cfg_cache = (None, None)
+        self._resident_policy = resident_mirror
         self._lifetimes_touched = False
-        self._stor = [None] * len(_SLOTS)
+        self._make_machine()
+        self.lazy_reset = bool(lazy_reset)
         self.size = size
         self.initial_snake_length = initial_snake_length
         self.on_death = on_death
@@ -419,31 +329,38 @@ class MultiSnake(object):
             if failures:
                 raise RuntimeError('There is no available locations to create snake!')
 
-    def _make_machine(self, num_envs: int, num_snakes: int):
-        """the argument block of the per-call launches, the output slabs and the step machine over them (the block is filled
-        in on first use: _ensure_call) — derived state: made by the constructor and again by __setstate__"""
-        from wurm_amd.envs._fast_step import _make_stepper
-        self._cfg_dirty = True
+    def _make_machine(self):
+        """Derived state, ALL of it: the argument block of the per-call launches (filled in on first use: _ensure_call), the
+        output slabs, the step machine over them and the role objects.  Whatever this method adds to the object is left out
+        of a copy / pickle and made again by this method on the other side."""
+        d = self.__dict__
+        before = set(d)
         self._mc, self._sl = _lib.MultiCall(), _lib.MultiSlabs()
         self._mc_addr = ctypes.addressof(self._mc)
         self._fs = fs = _make_stepper('wurm_multi_step_slot', self._mc_addr, ctypes.addressof(self._sl))
-        fs.num_envs, fs.num_agents = num_envs, num_snakes
+        fs.num_envs, fs.num_agents = self.num_envs, self.num_snakes
         fs.alias_free = self._alias_free
         fs.dev_index = -1 if self.device.index is None else self.device.index
+        self._mir = Mirror(self._mc, self._mc_addr, ('wurm_multi_resident_bytes', 'wurm_multi_resident_size',
+                                                     'wurm_multi_resident_flush'), self._resident_policy,
+                           self._MIRROR_WORDS, True, self.device)
+        self._masks, self._reset_obs, self._out = Masks(fs, self._mc), ResetObs(self), Outputs(self)
+        self._watched = ()           # (tensor, version) of state tensors the caller holds: in-place edits make the mirror stale
+        self._pend = None            # (N) bytes: the kernels' own copy of the last step's dones['__all__']
+        self._abuf = None            # (K, N) int64: the action block of a step whose K action tensors had to be stacked
+        self._cfg_dirty, self._cfg_cache, self._mc_cfg, self._mc_ready = True, (None, None), None, False
+        self._stor = [None] * len(_SLOTS)
+        self._info = self._keys = self._get_device = None
+        self._machine_made = frozenset(set(d) - before) | {'_machine_made'}
 
     # ------------------------------------------------------------------ copy / pickle
-    # The reference's env is a plain attribute bag: copy.deepcopy(env) and pickle work on it (multi_snake.py:56-160).  The
-    # ctypes blocks, the step machine, the mirror and the output slabs are derived state: left out here and rebuilt on the
-    # other side, after the postponed reset and a lazy mirror have been applied to the tensors that ARE the state.
-    _DERIVED = ('_mc', '_sl', '_mc_addr', '_fs', '_pend', '_cfg_cache', '_mc_cfg', '_mc_ready', '_mc_mode', '_mirror',
-                '_mirror_off', '_lazy_mirror', '_mirror_why', '_watched', '_write_outs', '_touches', '_chk', '_chk_has_after',
-                '_chk_armed_at', '_chk_void_at', '_check_calls', '_check_step', '_slab', '_stor', '_keys', '_get_device',
-                '_rewards_t', '_boost_t', '_rewards_at', '_boost_at', '_rewards_src', '_info', '_cfg_dirty',
-                '_reset_obs_probe', '_reset_obs_drops', '_lazy_obs_mode', '_lazy_obs_ref', '_abuf')
+    # The reference's env is a plain attribute bag: copy.deepcopy(env) and pickle work on it (multi_snake.py:56-160).  What
+    # _make_machine made is left out here and made again on the other side, after the postponed reset and a lazy mirror
+    # have been applied to the tensors that ARE the state.
 
     def __getstate__(self):
         self._state()   # (applies a postponed reset, writes a lazy mirror out)
-        st = {k: v for k, v in self.__dict__.items() if k not in self._DERIVED}
+        st = {k: v for k, v in self.__dict__.items() if k not in self._machine_made}
         st['_copy_call'] = int(self._fs.call)
         st['_copy_rewards'], st['_copy_boost'] = self.rewards, self.boost_this_step
         return st
@@ -452,11 +369,7 @@ class MultiSnake(object):
         st = dict(st)
         call, rewards, boost = st.pop('_copy_call'), st.pop('_copy_rewards'), st.pop('_copy_boost')
         self.__dict__.update(st)
-        self._make_machine(self.num_envs, self.num_snakes)
-        self._pend, self._cfg_cache, self._stor = None, (None, None), [None] * len(_SLOTS)
-        self._mirror_off = self._resident_policy is False
-        self._lazy_mirror = self._resident_policy != 'eager' and MultiSnake._lazy_mirror
-        self._mirror_why = 'resident_mirror=False' if self._resident_policy is False else 'no step yet'
+        self._make_machine()
         self._fs.call = call
         self._fs.lazy_ok = self._lazy_ok()
         self.rewards, self.boost_this_step = rewards, boost
@@ -520,28 +433,20 @@ class MultiSnake(object):
     @property
     def rewards(self) -> torch.Tensor:
         """reference :105/:478: (num_envs*num_snakes,) float, env-major — a view of the last step's output block"""
-        st = self._fs.steps
-        if self._rewards_at != st:  # (the env-major block at the start of the last step's packed floats)
-            self._rewards_t, self._rewards_at = self._slab[0][self._fs.slot - 1].view(-1)[:self.num_envs * self.num_snakes], st
-        elif self._rewards_t is None:  # (after a rollout: its last step's (K, N) block, env-major on demand)
-            self._rewards_t, self._rewards_src = self._rewards_src.t().reshape(-1), None
-        return self._rewards_t
+        return self._out.rewards()
 
     @rewards.setter
     def rewards(self, value):
-        self._rewards_t, self._rewards_at = value, self._fs.steps
+        self._out.rewards_t, self._out.rewards_at = value, self._fs.steps
 
     @property
     def boost_this_step(self) -> torch.Tensor:
         """reference :104: (num_envs*num_snakes,) env-major — a view of the last step's output block"""
-        st = self._fs.steps
-        if self._boost_at != st:
-            self._boost_t, self._boost_at = self._slab[1][self._fs.slot - 1].view(-1)[:self.num_envs * self.num_snakes], st
-        return self._boost_t
+        return self._out.boost()
 
     @boost_this_step.setter
     def boost_this_step(self, value):
-        self._boost_t, self._boost_at = value, self._fs.steps
+        self._out.boost_t, self._out.boost_at = value, self._fs.steps
 
     def _sync_state(self):
         """the state tensors as the step machine knows them (its own storage-use-count check, wurm_torch_alias_free)"""
@@ -567,76 +472,24 @@ class MultiSnake(object):
         fs = self._fs
         fs.pending = False
         self._launch_reset(self._pend, None, _lib.OBS_NONE, 0, fs.pend_call, None)
-        if self._lazy_obs_ref is not None:   # the dict that reset returned, if the caller still holds it: filled NOW, while
-            lz = self._lazy_obs_ref()        # the state is what the reset left
-            if lz is not None:
-                lz._fill()
-            self._lazy_obs_ref = None
-
-    def _settle_reset_obs(self, lz):
-        """fills the _LazyResetObs `lz`: the postponed reset applied (if it still is postponed), then the observation of the
-        mode that reset was called in — what the reference's reset returned (:834-836).  The caller reads, or still holds,
-        what reset returns after all: back to precomputing it in the step launch."""
-        self._lazy_obs_ref = None
-        if self._pending:
-            self._flush()
-        obs = self._observe(lz._mode)
-        dict.update(lz, obs)
-        self._lazy_obs_mode = False
-        self._reset_obs_drops = -(1 << 20)   # (no flapping: a caller that reads it once is a caller that reads it)
-        self._fs.want_obs_after = True
+        self._reset_obs.before_change()   # (the dict that reset returned, if still held: filled while the state is what the
+                                          # reset left)
 
     def _reset_obs_bookkeeping(self):
-        """in front of a step: did the caller keep what the last reset(done) returned?"""
-        probe, self._reset_obs_probe = self._reset_obs_probe, None
-        if probe is not None:
-            # the references of a dict nobody else holds: the slab's list of precomputed dicts, `probe`, getrefcount's argument
-            if sys.getrefcount(probe) <= 3:
-                self._reset_obs_drops += 1
-                if self._reset_obs_drops >= self._RESET_OBS_DROPS and not self._half:
-                    self._lazy_obs_mode = True
-            else:
-                self._reset_obs_drops = min(self._reset_obs_drops, 0)
-        if self._lazy_obs_ref is not None:
-            lz = self._lazy_obs_ref()
-            self._lazy_obs_ref = None
-            if lz is not None:
-                lz._fill()   # still held: the state is about to change
+        """in front of a step: did the caller keep what the last reset(done) returned?  (the name the protocol tests patch)"""
+        self._reset_obs.before_step()
 
-    # ---- the resident mirror (include/wurm_hip.h: wurm_multi_call.resident; protocol as in envs/_fast_step.py)
+    # ---- the resident mirror (wurm_amd/envs/_mirror.py; include/wurm_hip.h: wurm_multi_call.resident).  Who holds a state
+    # tensor is this class's business: `_watched`.
 
     def _write_out(self):
         """foods / heads / bodies from a lazy mirror (which stays current)"""
-        c = self._mc
-        if c is not None and c.resident and c.resident_lazy and c.resident_valid:
-            rc = _lib.call(self.device.index, _lib.lib().wurm_multi_resident_flush, self._mc_addr,
-                           _lib.stream_ptr(self.device.index))
-            _lib.check(rc, 'wurm_multi_resident_flush')
-            # a caller that keeps looking at the state (experiments/speeds.py:30-38: check_consistency() every step) pays a
-            # whole-state write per look in the lazy form: from the second one on the steps write the tensors themselves
-            self._write_outs += 1
-            if self._write_outs >= 2 and self._resident_policy is None:
-                c.resident_lazy = 0
-                self._lazy_mirror = False
-                self._mirror_why = 'adaptive: the state was looked at twice, every step writes the tensors from now on'
+        self._mir.write_out()
 
     def _touch(self):
         """something other than the step launch is about to read or write the state tensors"""
-        self._write_out()
-        self._chk_fresh = False
-        c = self._mc
-        if c is not None:
-            if c.resident and c.resident_valid:
-                # a loop in which (nearly) every step is followed by something that writes the state some other way (an
-                # eager reset: experiments/speeds.py's check_consistency() flushes the postponed one every step) rebuilds
-                # the mirror every step for nothing: switch it off for this env object
-                self._touches += 1
-                if self._resident_policy is None and self._touches >= 8 and 2 * self._touches >= self._steps:
-                    self._mirror_off, self._mirror = True, None
-                    c.resident = None
-                    self._mirror_why = ('adaptive: the state was written by something other than the step launch after %d '
-                                        'of %d steps' % (self._touches, self._steps))
-            c.resident_valid = 0
+        self._masks.void()
+        self._mir.touch(self._fs.steps)
 
     def _escape(self, t):
         """The caller holds the state tensor `t` from now on: it is brought up to date, written by every step (no lazy form
@@ -644,19 +497,12 @@ class MultiSnake(object):
         if self._watched:
             self._watch_ok()   # (an edit through a tensor the caller already holds must not be forgotten when its version is
                                # taken again below: edit, look, step would step on a stale mirror)
-        self._write_out()
-        self._chk_fresh = False
-        if self._mc is not None:
-            self._mc.resident_lazy = 0
-        self._lazy_mirror = False
-        if not self._mirror_off:
-            self._mirror_why = 'the caller holds a state tensor: every step writes them, in-place edits are watched'
+        self._mir.write_out()
+        self._masks.void()
+        self._mir.holds()
         ver = _version_of(t) if isinstance(t, torch.Tensor) else -1
         if ver < 0:
-            self._mirror_off, self._mirror = True, None
-            self._mirror_why = 'a state tensor has no version counter (inference mode): cannot be watched'
-            if self._mc is not None:
-                self._mc.resident, self._mc.resident_valid = None, 0
+            self._mir.unwatchable()
             return
         self._watched = tuple((x, v) for x, v in self._watched if x is not t) + ((t, ver),)
 
@@ -670,8 +516,9 @@ class MultiSnake(object):
             self._touch()
             self._watched = tuple((x, _version_of(x)) for x, _ in self._watched)
             if any(v < 0 for _, v in self._watched):
-                self._mirror_off, self._mirror, self._watched = True, None, ()
-                self._mc.resident, self._mc.resident_valid = None, 0
+                self._watched = ()
+                self._mir.drop()
+                self._mc.resident_valid = 0
         return ok
 
     def mirror_state(self) -> dict:
@@ -679,11 +526,7 @@ class MultiSnake(object):
         (steps read the mirror and write the tensors) / 'lazy' (steps do not write them; they are written out when something
         looks at them), `why`, `policy` (the `resident_mirror` keyword; None = automatic), `current` (the mirror describes
         the state; False: the next step rebuilds it)."""
-        c = self._mc
-        on = c is not None and bool(c.resident) and self._mirror is not None
-        return {'state': 'off' if not on else ('lazy' if c.resident_lazy else 'eager'), 'why': self._mirror_why,
-                'policy': self._resident_policy, 'current': bool(on and c.resident_valid),
-                'bytes': int(self._mirror.numel()) if on else 0}
+        return self._mir.state()
 
     def _log(self, msg: str):
         if self.verbose > 0:
@@ -712,8 +555,8 @@ class MultiSnake(object):
             if raw:  # (not through the descriptor: nobody else holds the normalised copy)
                 setattr(self, '_' + name, t)
                 self._sync_state()
-                self._state_dirty = True
-                if '_' + name in _MIRRORED and self._mc is not None:
+                self._fs.ok = False   # (the next step re-reads the pointers)
+                if '_' + name in _MIRRORED:
                     self._mc.resident_valid = 0
             else:
                 fresh = self._last_fresh
@@ -834,102 +677,20 @@ class MultiSnake(object):
         ks = [str(i) for i in range(K)]
         self._keys = tuple([p + k for k in ks] for p in ('agent_', 'snake_collision_', 'edge_collision_', 'food_',
                                                          'boost_', 'size_'))
-        # the resident mirror of foods / heads / bodies (large batches): the launch reads it instead of them;
-        # lazy (they are not written either) as long as the caller has never got hold of one of them
-        size_fn = _lib.lib().wurm_multi_resident_bytes if self._resident_policy is None else \
-            _lib.lib().wurm_multi_resident_size
-        nbytes = 0 if self._mirror_off else int(size_fn(_lib.i64(N), K, S))
-        if not self._mirror_off:
-            self._mirror_why = 'on' if nbytes > 0 else 'batch below the threshold (2^20 cells), or shape not served'
-        if nbytes > 0:
-            self._mirror = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            c.resident, c.resident_valid = self._mirror.data_ptr(), 0
-            c.resident_lazy = int(self._lazy_mirror and not self._watched)
-            # check_consistency()'s masks can come out of the step launch (the image it steps is its own): asked for
-            # once the caller has called check_consistency(), dropped again if it stops doing so
-            self._chk = torch.empty((2, N), dtype=torch.int32, device=dev)
+        # the resident mirror of foods / heads / bodies (large batches): the launch reads it instead of them; lazy (they are
+        # not written either) as long as the caller has never got hold of one of them (holds() has ended that by then, so
+        # `held` is not passed: a mirror set up under a tensor already held says 'on', as it always has)
+        self._mir.setup(True, (_lib.i64(N), K, S), self._fs.steps, False, dev)
+        if self._mir.buf is not None:
+            # check_consistency()'s masks can come out of the step launch (the image it steps is its own)
+            self._masks.buf = torch.empty((2, N), dtype=torch.int32, device=dev)
         return c
-
-    def _arm_masks(self):
-        """check_consistency()'s masks from inside the step launch: asked for while the caller keeps calling that method"""
-        c = self._mc
-        if self._chk is None:
-            return
-        want = self._check_calls > 0 and self._fs.steps - self._check_step <= 64
-        if want != bool(c.check_mask):
-            c.check_mask = self._chk[0].data_ptr() if want else None
-            c.check_mask_after = self._chk[1].data_ptr() if want else None
-            self._chk_armed_at = self._fs.steps if want else 1 << 62  # (steps from here on write them)
-
-    def _new_slab(self):
-        """Fresh output tensors for the next R steps in four allocations, and the R x (8 K + 1) per-agent views and 4 dicts
-        `step` returns (reference :701-729) made ONCE per slab — a view object per row was most of what a step cost on the
-        host.  A slab is never written twice; it is released when the last tensor carved from it is."""
-        N, K, dev, fs = self.num_envs, self.num_snakes, self.device, self._fs
-        if self._slab is not None and fs.steps > 0:
-            _, _ = self.rewards, self.boost_this_step  # (views of the slab that is being replaced: made while it is at hand)
-        c = self._mc
-        mode = self.observation_mode
-        c.obs_mode, c.obs_n, o = self._obs_args(mode)
-        inner = tuple(o.shape[2:])
-        self._mc_mode = mode
-        elems = int(torch.Size(inner).numel())
-        want_after = bool(fs.want_obs_after)
-        per_step = K * N * (4 * elems * (2 if want_after else 1) + 24 + 7) + N
-        # 64 MB per slab at most: a caller that drops what a step returned before the next one gets the SAME block back from
-        # torch's allocator, and one call's outputs (123 MB at cfg4 'full': one step per slab) then stay in the 256 MB
-        # Infinity Cache; a slab of several such steps would stream to HBM (measured: 39 against 35 us per iteration at cfg4)
-        R = max(1, min(64, (64 << 20) // max(per_step, 1)))
-        # TWO allocations for the slab's four blocks (round 6: four torch.empty were 10 of the 28 us a step of cfg4 'full' — one
-        # step per slab — cost on the host, which is what bounded that loop): one block of floats (rewards / food / sizes,
-        # observations, reset observations; each part on a 256-byte boundary) and the flags on their own — their version
-        # counter is what proves `dones['__all__']` unmodified, and an in-place edit of an observation must not touch it
-        n_of, n_obs = R * 6 * K * N, R * K * N * elems
-        n_of_pad, n_obs_pad = (n_of + 63) & ~63, (n_obs + 63) & ~63
-        floats = torch.empty(n_of_pad + n_obs_pad + (n_obs if want_after else 0), dtype=torch.float32, device=dev)
-        of = floats[:n_of].view(R, 6 * K, N)
-        obs = floats[n_of_pad:n_of_pad + n_obs].view((R, K, N) + inner)
-        after = floats[n_of_pad + n_obs_pad:].view((R, K, N) + inner) if want_after else None
-        ob = torch.empty((R, 7 * K + 1, N), dtype=torch.bool, device=dev)
-        sl = self._sl
-        sl.out_f32, sl.out_u8, sl.obs, sl.steps, sl.obs_elems = of.data_ptr(), ob.data_ptr(), obs.data_ptr(), R, elems
-        sl.obs_after = after.data_ptr() if after is not None else None
-        self._slab = (of.unbind(0), ob.unbind(0))
-        try:
-            fs.slab_version = ob._version
-        except RuntimeError:   # allocated under torch.inference_mode(): no version counters, so no deferral (eager resets)
-            fs.slab_version = -1
-        # what callers read every step — observations, rewards, dones — is carved now (row_views: ~0.3 us per tensor); the
-        # 5 K tensors of `info` when somebody looks (_LazyInfo)
-        K3, K4 = 3 * K, 4 * K
-        ofs, obs_ = self._slab
-        rf = _lib.row_views(of, 2, K3, K4)                      # rewards (agent-major rows 3K .. 4K)
-        ob2 = ob.view(R, 7 * K + 1, N)
-        rd = _lib.row_views(ob2, 2, K3, K4)                     # dones
-        ra = _lib.row_views(ob2, 2, 7 * K, 7 * K + 1)           # all_done
-        ov = _lib.row_views(obs, 2)
-        av = _lib.row_views(after, 2) if after is not None else None
-        k_agent, k_snake, k_edge, k_food, k_boost, k_size = self._keys
-        info_keys = (k_snake, k_edge, k_food, k_boost, k_size)
-        outs, done2s, afters = [], [], []
-        for i in range(R):
-            f, b = rf[i * K:(i + 1) * K], rd[i * K:(i + 1) * K] + [ra[i]]
-            dones_out = dict(zip(k_agent, b[:K]))
-            dones_out['__all__'] = b[K]
-            info = _LazyInfo((ofs[i], obs_[i], info_keys, K))
-            outs.append((OrderedDict(zip(k_agent, ov[i * K:(i + 1) * K])), dict(zip(k_agent, f)), dones_out, info))
-            done2s.append(b[K])
-            if av is not None:
-                afters.append(OrderedDict(zip(k_agent, av[i * K:(i + 1) * K])))
-        fs.outs, fs.done2s, fs.obs_afters = outs, done2s, (afters if av is not None else None)
-        fs.R, fs.slot = R, 0
-        fs.lazy_ok = self._lazy_ok()
-        self._arm_masks()
 
     def step(self, actions: Dict[str, torch.Tensor]) -> Tuple[Dict[str, torch.Tensor], dict, dict, dict]:
         """reference :462-731.  One launch (wurm_multi_step_slot) from the step machine; the four dicts it returns were
         built when the output slab was."""
-        if self._reset_obs_probe is not None or self._lazy_obs_ref is not None:
+        ro = self._reset_obs
+        if ro.probe is not None or ro.ref is not None:
             self._reset_obs_bookkeeping()
         if self._watched and self._alias_free():
             # The caller read a state attribute earlier (experiments/multiagent.py:531 reads `env.heads`) and has let go of
@@ -970,20 +731,7 @@ class MultiSnake(object):
                 raise RuntimeError('Must have the same number of actions as environments.')
 
         N, K, dev, fs = self.num_envs, self.num_snakes, self.device, self._fs
-        # reference :492: stack in dict order -> (K, N); the kernel reads agent i's action of env e at [i*N + e].
-        # Rows of one (K, N) int64 tensor (e.g. `tape[t, i]`) are used where they lie.
-        vals = list(actions.values())
-        a0 = vals[0]
-        a_ptr = a0.data_ptr() if (a0.dtype is torch.long and a0.device == dev) else 0
-        if a_ptr:
-            row = 8 * N
-            for i, v in enumerate(vals):
-                if v.dtype is not torch.long or v.dim() != 1 or not v.is_contiguous() or v.data_ptr() != a_ptr + i * row:
-                    a_ptr = 0
-                    break
-        if not a_ptr:
-            vals = torch.stack([v.reshape(N) for v in vals]).to(device=dev, dtype=torch.long).contiguous()
-            a_ptr = vals.data_ptr()
+        a_ptr, block = _action_block(list(actions.values()), N, dev)  # (`block`: alive until the launch has been queued)
         # (if anything below raises, the postponed reset and the counter are still owed: the machine consumes them only
         # once the launch has been accepted)
         c = self._ensure_call()
@@ -995,12 +743,11 @@ class MultiSnake(object):
                 foods, heads, bodies, dones, orientations, colours, _ = self._step_state()
             finally:
                 fs.pending = pend
-            c.foods, c.heads, c.bodies = foods.data_ptr(), heads.data_ptr(), bodies.data_ptr()
-            c.dones, c.orientations, c.colours = dones.data_ptr(), orientations.data_ptr(), colours.data_ptr()
-        if fs.slot >= fs.R or self.observation_mode != self._mc_mode or (fs.want_obs_after and fs.obs_afters is None):
-            self._new_slab()
+            _bind_state(c, (foods, heads, bodies, dones, orientations, colours))
+        if fs.slot >= fs.R or self.observation_mode != self._out.mode or (fs.want_obs_after and fs.obs_afters is None):
+            self._out.new()
         else:
-            self._arm_masks()
+            self._masks.arm()
         cfg = self._cfg()
         if cfg is not self._mc_cfg:
             c.cfg = self._mc_cfg = cfg
@@ -1057,44 +804,36 @@ class MultiSnake(object):
         if self._pending:
             self._flush()
         c = self._ensure_call() if T > 0 else self._mc
-        if c is not None and c.resident and self._watched:
+        if c.resident and self._watched:
             self._watch_ok()
-        mirrored = c is not None and bool(c.resident)
+        mirrored = bool(c.resident)
         if mirrored:
-            foods, heads, bodies, dones, orientations, colours, boost = self._step_state()
+            foods, heads, bodies, dones, orientations, colours, boost = state = self._step_state()
             # (the argument block names the tensors for wurm_multi_resident_flush — a look at the state right after this
             # rollout writes the mirror out through it, whether or not a step() has ever filled it in)
-            c.foods, c.heads, c.bodies = foods.data_ptr(), heads.data_ptr(), bodies.data_ptr()
-            c.dones, c.orientations, c.colours = dones.data_ptr(), orientations.data_ptr(), colours.data_ptr()
-            self._state_dirty = False
-            self._chk_fresh = False  # (the masks of the last step launch describe an older state)
+            _bind_state(c, state[:6])
+            self._masks.void()  # (the masks of the last step launch describe an older state)
+            tail = (c.resident, self._mc_addr + _lib.MultiCall.resident_valid.offset, int(c.resident_lazy))
         else:
             foods, heads, bodies, dones, orientations, colours, boost = self._state()
+            tail = (None, None)
         m, n, obs1 = self._obs_args(self.observation_mode if return_observations else None)
         obs = torch.empty((T,) + tuple(obs1.shape), dtype=torch.float32, device=dev) if obs1 is not None else None
         out_f = torch.empty((T, 3, K, N), dtype=torch.float32, device=dev)
         out_b = torch.empty((T, 4, K, N), dtype=torch.bool, device=dev)
         all_done = torch.empty((T, N), dtype=torch.bool, device=dev)
         cfg = self._cfg()
-        if mirrored:
-            rc = _lib.call(self.device.index, _lib.lib().wurm_multi_rollout_resident,
-                _lib.ptr(foods), _lib.ptr(heads), _lib.ptr(bodies), _lib.ptr(dones), _lib.ptr(orientations),
-                _lib.ptr(colours), _lib.ptr(boost), _lib.ptr(actions), _lib.ptr(out_f), _lib.ptr(out_b), _lib.ptr(all_done),
-                _lib.ptr(obs), m, n, _lib.i64(N), K, S, _lib.i64(T), ctypes.byref(cfg), _lib.u64(self.seed),
-                _lib.u64(self._next_call(2 * T)), _lib.i64(self.env_offset), c.resident,
-                self._mc_addr + _lib.MultiCall.resident_valid.offset, int(c.resident_lazy),
-                _lib.stream_ptr(self.device.index))
-        else:
-            rc = _lib.call(self.device.index, _lib.lib().wurm_multi_rollout,
-                _lib.ptr(foods), _lib.ptr(heads), _lib.ptr(bodies), _lib.ptr(dones), _lib.ptr(orientations),
-                _lib.ptr(colours), _lib.ptr(boost), _lib.ptr(actions), _lib.ptr(out_f), _lib.ptr(out_b), _lib.ptr(all_done),
-                _lib.ptr(obs), m, n, _lib.i64(N), K, S, _lib.i64(T), ctypes.byref(cfg), _lib.u64(self.seed),
-                _lib.u64(self._next_call(2 * T)), _lib.i64(self.env_offset), None, None, _lib.stream_ptr(self.device.index))
+        fn = _lib.lib().wurm_multi_rollout_resident if mirrored else _lib.lib().wurm_multi_rollout
+        ptr = _lib.ptr
+        rc = _lib.call(self.device.index, fn, ptr(foods), ptr(heads), ptr(bodies), ptr(dones), ptr(orientations), ptr(colours),
+                       ptr(boost), ptr(actions), ptr(out_f), ptr(out_b), ptr(all_done), ptr(obs), m, n, _lib.i64(N), K, S, _lib.i64(T),
+                       ctypes.byref(cfg), _lib.u64(self.seed), _lib.u64(self._next_call(2 * T)), _lib.i64(self.env_offset),
+                       *tail, _lib.stream_ptr(self.device.index))
         _lib.check(rc, 'MultiSnake.rollout')
         if T > 0:
             # (reference :105: env-major; the last step's rewards are agent-major here — transposed when somebody asks for
             # the attribute, not by a kernel between two rollout launches)
-            self._rewards_src, self._rewards_t, self._rewards_at = out_f[-1, 0], None, self._fs.steps
+            self._out.rewards_src, self._out.rewards_t, self._out.rewards_at = out_f[-1, 0], None, self._fs.steps
         if self._lifetimes_touched:  # (else it is all zeros already: env_lifetimes' docstring)
             self._env_lifetimes.zero_()
         if self._half:
@@ -1114,8 +853,7 @@ class MultiSnake(object):
         of its own `dones['__all__']`) on the resident mirror the masks come from that step's launch; anything else — the
         state read from the fp32 tensors, looked at or edited since — runs the checker over the tensors."""
         from wurm_amd.utils import _raise_for, _or_reduce
-        self._check_calls += 1
-        self._check_step = self._steps
+        self._masks.asked()
         err = self._step_check_mask()
         if err is not None:
             if not bool(err.any()):
@@ -1139,29 +877,24 @@ class MultiSnake(object):
     def _step_check_mask(self):
         """(N) int32 masks of the state as it is now, computed inside the last step's launch (wurm_multi_call.check_mask /
         check_mask_after), or None if they do not apply; -1 marks an env the launch could not vouch for"""
-        c = self._mc
-        self._arm_masks()   # (from the next step on, if they are not being written yet)
-        if self._watched and c is not None and not self._watch_ok():
+        self._masks.arm()   # (from the next step on, if they are not being written yet)
+        if self._watched and not self._watch_ok():
             return None                   # an alias the caller holds was edited in place since the launch (_touch() ran)
-        if not self._chk_fresh or c is None or not c.resident or not c.resident_valid:
-            return None
-        if not self._pending:
-            return self._chk[0]
-        if self._chk_has_after:       # the postponed reset of the step's own mask: what obs_after observed
-            return self._chk[1]
-        # postponed, but the launch did not build that state: envs the reset rebuilds are not vouched for
-        return self._chk[0].masked_fill(self._pend != 0, -1)
+        return self._masks.current(self._pend)
 
     # ------------------------------------------------------------------ reset
 
+    def _call_reset(self, what, state, done, status, boost, obs, m, n, num_envs, cfg, call):
+        """wurm_multi_reset over the six tensors `state` (this object's, or a fresh batch's)"""
+        rc = _lib.call(self.device.index, _lib.lib().wurm_multi_reset, *[_lib.ptr(t) for t in state], _lib.ptr(done),
+                       _lib.ptr(status), _lib.ptr(boost), _lib.ptr(obs), m, n, _lib.i64(num_envs), self.num_snakes, self.size,
+                       ctypes.byref(cfg), _lib.u64(self.seed), _lib.u64(call), _lib.i64(self.env_offset), None,
+                       _lib.stream_ptr(self.device.index))
+        _lib.check(rc, what)
+
     def _launch_reset(self, done: torch.Tensor, obs, m, n, call, status):
-        foods, heads, bodies, dones, orientations, colours, boost = self._state()
-        rc = _lib.call(self.device.index, _lib.lib().wurm_multi_reset,
-            _lib.ptr(foods), _lib.ptr(heads), _lib.ptr(bodies), _lib.ptr(dones), _lib.ptr(orientations),
-            _lib.ptr(colours), _lib.ptr(done), _lib.ptr(status), _lib.ptr(boost), _lib.ptr(obs), m, n,
-            _lib.i64(self.num_envs), self.num_snakes, self.size, ctypes.byref(self._cfg()), _lib.u64(self.seed),
-            _lib.u64(call), _lib.i64(self.env_offset), None, _lib.stream_ptr(self.device.index))
-        _lib.check(rc, 'MultiSnake.reset')
+        state = self._state()
+        self._call_reset('MultiSnake.reset', state[:6], done, status, state[6], obs, m, n, self.num_envs, self._cfg(), call)
 
     def _reset_kernel(self, done: torch.Tensor, observe: bool, want_status: bool = False):
         if self._pending:
@@ -1192,21 +925,20 @@ class MultiSnake(object):
             # (the machine checks that `done` is the very tensor the last step returned, unmodified, that nothing has consumed a
             # counter since, and that nobody else holds a state tensor: _alias_free / wurm_torch_alias_free)
             if fs.last_fresh:
-                if return_observations and self._lazy_obs_mode:
+                ro = self._reset_obs
+                if return_observations and ro.lazy_mode:
                     # the caller has been discarding what reset returns: postponed without the precomputed observation; the
                     # dict fills itself if it is looked at after all (_LazyResetObs)
                     if fs.reset_lazy(done, False) is None:
-                        self._chk_has_after = False
-                        lz = _LazyResetObs(self, self.observation_mode)
-                        self._lazy_obs_ref = weakref.ref(lz)
-                        return lz
+                        self._masks.has_after = False
+                        return ro.hand_out(self.observation_mode)
                 else:
                     obs = fs.reset_lazy(done, return_observations)
                     if obs is not NotImplemented:
                         # env_lifetimes is all zeros here (nobody has asked for it): `env_lifetimes[done] = 0` (:797) is a no-op
-                        self._chk_has_after = had_after  # the launch also left the masks of the state this reset produces
+                        self._masks.has_after = had_after  # the launch also left the masks of the state this reset produces
                         if obs is not None:
-                            self._reset_obs_probe = obs
+                            ro.probe = obs
                             if self._half:
                                 obs = OrderedDict((k, v.to(torch.half)) for k, v in obs.items())
                         return obs
@@ -1237,12 +969,8 @@ class MultiSnake(object):
         status = torch.zeros(1, dtype=torch.int32, device=dev)
         cfg = _lib.MultiConfig.from_buffer_copy(self._cfg())  # a copy: the cached block stays as it is
         cfg.respawn_any = 0
-        rc = _lib.call(self.device.index, _lib.lib().wurm_multi_reset, 
-            _lib.ptr(foods), _lib.ptr(heads), _lib.ptr(bodies), _lib.ptr(dones), _lib.ptr(orientations),
-            _lib.ptr(colours), _lib.ptr(ones), _lib.ptr(status), None, None, _lib.OBS_NONE, 0, _lib.i64(num_envs), K,
-            S, ctypes.byref(cfg), _lib.u64(self.seed), _lib.u64(self._next_call()), _lib.i64(self.env_offset), None,
-            _lib.stream_ptr(self.device.index))
-        _lib.check(rc, 'MultiSnake._create_envs')
+        self._call_reset('MultiSnake._create_envs', (foods, heads, bodies, dones, orientations, colours), ones, status, None,
+                         None, _lib.OBS_NONE, 0, num_envs, cfg, self._next_call())
         if int(status.item()):
             raise RuntimeError('There is no available locations to create snake!')
         return (foods, heads, bodies), orientations

@@ -8,10 +8,14 @@ returns from n-step to generalised advantage estimation (the reference's `--gae-
 The log line has the reference's columns (main.py:252-316: episodes, reward_rate, policy_entropy, edge_collisions,
 self_collisions, avg_size and their smoothed `ewm_` versions) and the mean and maximum return, length and final snake
 size of the episodes that ended since the last line: `wurm_amd.rl.RolloutStats` keeps them on the device, two more
-launches per window, and is read once per line.
+launches per window, and is read once per line.  `--save-video PATH` records the first `--video-envs` envs of every
+`--video-interval`-th window (a .gif or .npy, or an .mp4 where ffmpeg is installed): those windows are replayed for the
+chosen envs after the fact (`env.record_start` / `env.record_frames`), the training launches are the same either way, and
+without the option nothing of it runs.
 
     python examples/a2c_fused_learner.py --num-envs 512 --steps 20000
     python examples/a2c_fused_learner.py --num-envs 512 --steps 20000 --gae-lambda 0.95
+    python examples/a2c_fused_learner.py --steps 20000 --save-video snake.gif --video-envs 4 --video-interval 100
 """
 import argparse
 import os
@@ -23,11 +27,13 @@ import torch  # noqa: E402
 
 from wurm_amd.agents import FeedforwardAgent  # noqa: E402
 from wurm_amd.envs import SingleSnake  # noqa: E402
+from wurm_amd.recording import WindowRecorder  # noqa: E402
 from wurm_amd.rl import FusedA2CLearner, RolloutStats  # noqa: E402
 
 
 def run(num_envs=512, size=9, observation='partial_2', steps=20000, update_steps=5, gamma=0.99, lr=1e-3, entropy=0.01,
-        log_interval=2000, seed=0, device='cuda', verbose=True, gae_lambda=None):
+        log_interval=2000, seed=0, device='cuda', verbose=True, gae_lambda=None, save_video=None, video_envs=4,
+        video_interval=1):
     torch.manual_seed(seed)
     env = SingleSnake(num_envs=num_envs, size=size, observation_mode=observation, device=device, seed=seed)
     state = env.reset()                                                     # main.py:195
@@ -35,9 +41,13 @@ def run(num_envs=512, size=9, observation='partial_2', steps=20000, update_steps
     learner = FusedA2CLearner(model, lr=lr, gamma=gamma, entropy_coef=entropy, max_grad_norm=0.5,
                               use_gae=gae_lambda is not None, gae_lambda=gae_lambda)        # multiagent.py:274-275
     stats = RolloutStats(env)                                               # :252-274, on the device
+    video = WindowRecorder(env, save_video, range(min(video_envs, num_envs)), video_interval) if save_video else None
     history, t0 = [], time.perf_counter()
-    for i_step in range(update_steps, steps + 1, update_steps):
+    for window, i_step in enumerate(range(update_steps, steps + 1, update_steps)):
+        rec = video.start(window) if video else None                                            # :184-186, 201-202
         out = env.policy_rollout(learner.params, state, update_steps, check=False)              # :207-227, fused
+        if rec is not None:
+            video.finish(rec, out['actions'])
         res = learner.update(state, out)                                                         # :229-245, fused
         state = out['state']
         stats.update(out)
@@ -50,6 +60,8 @@ def run(num_envs=512, size=9, observation='partial_2', steps=20000, update_steps
             history.append(row)
             if verbose:
                 print(' '.join(f'{k}={v:.4g}' for k, v in row.items()))
+    if video:
+        video.close()
     return history
 
 
@@ -62,6 +74,10 @@ if __name__ == '__main__':
     ap.add_argument('--update-steps', type=int, default=5)
     ap.add_argument('--lr', type=float, default=1e-3)
     ap.add_argument('--gae-lambda', type=float, default=None, help='GAE with this lambda instead of n-step returns')
+    ap.add_argument('--save-video', default=None, metavar='PATH', help='record envs of the fused windows (.gif / .npy / .mp4)')
+    ap.add_argument('--video-envs', type=int, default=4, metavar='K', help='the first K envs are recorded')
+    ap.add_argument('--video-interval', type=int, default=1, help='every this many windows one is recorded')
     args = ap.parse_args()
     run(args.num_envs, args.size, args.observation, args.steps, args.update_steps, lr=args.lr,
-        gae_lambda=args.gae_lambda)
+        gae_lambda=args.gae_lambda, save_video=args.save_video, video_envs=args.video_envs,
+        video_interval=args.video_interval)

@@ -795,6 +795,31 @@ int wurm_rollout_stats(const float *rewards, const uint8_t *dones, const uint8_t
                        double *table, void *workspace, int64_t workspace_bytes, int64_t num_envs, int64_t num_steps,
                        int64_t num_members, int initial_size, double alpha, void *stream);
 
+/* ---- frames of a fused window, after the fact (wurm_amd/csrc/rollout_frames.hpp) --------------------------------------
+ * A window of wurm_single_rollout / wurm_*_policy_rollout* (and the SimpleGridworld forms) is a pure function of an env's
+ * start state, its id env_offset + index, seed, the window's first call counter call0 and the SANITISED actions the launch
+ * returned.  These entry points re-run it for num_select chosen envs, one wave each, in one launch, and write what
+ * `_get_rgb()` shows in front of every step; the window's own kernels are untouched and pay nothing.
+ *   start        (num_select, C, S, S) float planes of the chosen envs before the window (C = 3; SimpleGridworld 2), read
+ *   select       (num_select) int64 env indices within the object; random draws use env_offset + select[j], never j
+ *   actions      (num_steps, num_envs) int64 as the window returned them; column select[j] is read (nullable if num_steps == 0)
+ *   frames       (num_steps + 1, num_select, 3, S, S) uint8, written: frame t is the env before step t (after step t - 1
+ *                and its reset); frame num_steps is the state the window leaves behind
+ *   final_state  (num_select, C, S, S) float planes after the last step and its reset, written
+ *   status       (num_select) bytes, written: 0 = replayed; 1 = select[j] is outside [0, num_envs): nothing of that env is
+ *                read, its frames and final planes are zeros
+ * Refused before any HIP call: a null required pointer, num_select <= 0, num_envs <= 0, num_steps < 0, size < 3
+ * (WURM_ERR_INVALID_ARG); size > 64, a size the class cannot reset (<= 8; SimpleGridworld <= 4), a start location off the
+ * grid, more than 2^31 - 1 selected envs (WURM_ERR_UNSUPPORTED).  One launch on `stream`. */
+int wurm_single_rollout_frames(const float *start, const int64_t *select, const int64_t *actions, uint8_t *frames,
+                               float *final_state, uint8_t *status, int64_t num_select, int64_t num_envs, int size,
+                               int64_t num_steps, uint64_t seed, uint64_t call0, int64_t env_offset, void *stream);
+
+int wurm_grid_rollout_frames(const float *start, const int64_t *select, const int64_t *actions, uint8_t *frames,
+                             float *final_state, uint8_t *status, int64_t num_select, int64_t num_envs, int size,
+                             int64_t num_steps, int start_y, int start_x, uint64_t seed, uint64_t call0,
+                             int64_t env_offset, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

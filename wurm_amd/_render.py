@@ -19,3 +19,20 @@ def frame(rgb_nchw, num_envs: int, render_args: dict, env: int = None) -> np.nda
         canvas = tiles.transpose(0, 2, 1, 3, 4).reshape(rows * S, cols * S, 3)
     px = render_args['size']
     return np.array(Image.fromarray(np.ascontiguousarray(canvas)).resize((px * cols, px * rows)))
+
+
+DEFAULT_RENDER_ARGS = {'num_rows': 1, 'num_cols': 1, 'size': 256}   # (single_snake.py:80-83)
+
+
+def tile_frames(frames, render_args: dict = None) -> np.ndarray:
+    """The pictures of recorded envs: `frames` is one (k, 3, S, S) frame or a (T, k, 3, S, S) clip of
+    `env.record_frames(...)['frames']` (array or tensor); each frame becomes the (H, W, 3) uint8 picture
+    `render('rgb_array')` makes for an env object of num_envs = k with these render_args (None: the reference's default,
+    one tile of 256 pixels).  Returns (H, W, 3) for one frame, (T, H, W, 3) for a clip."""
+    a = frames.cpu().numpy() if hasattr(frames, 'cpu') else np.asarray(frames)
+    args = DEFAULT_RENDER_ARGS if render_args is None else render_args
+    if a.ndim == 4:
+        return frame(a, a.shape[0], args)
+    if a.ndim != 5:
+        raise ValueError(f'tile_frames: expected (k, 3, S, S) or (T, k, 3, S, S), got {a.shape}')
+    return np.stack([frame(f, f.shape[0], args) for f in a])

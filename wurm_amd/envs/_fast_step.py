@@ -27,11 +27,11 @@ time per call, not by the GPU, so:
     then on every step writes it), any other entry point goes through `_touch()`, a tensor the caller holds is watched for
     in-place edits through its version counter (DESIGN.md §5, §7 deviation 9).
 
-`reset`, `rollout`, `_get_rgb` and the common part of `policy_rollout` are the mixin's as well: the two classes differ there in
-names and in SimpleGridworld's start location only.
+`reset`, `rollout`, `_get_rgb`, `record_start` / `record_frames` and the common part of `policy_rollout` are the mixin's as
+well: the two classes differ there in names and in SimpleGridworld's start location only.
 
 The host class provides: num_envs, size, device, seed, env_offset, observation_mode, lazy_reset, _mode_cache, _CHANNELS,
-_NAME, _STEP_SLOT / _ROLLOUT_FNS (plain, with a mirror) / _POLICY_FN (entry point names), _FLAG_KEYS (result keys of the flag
+_NAME, _STEP_SLOT / _ROLLOUT_FNS (plain, with a mirror) / _POLICY_FN / _FRAMES_FN (entry point names), _FLAG_KEYS (result keys of the flag
 rows an entry point writes), _BAD_STATUS, _parse_mode(mode) -> (mode code, n), _obs_shape(mode), _observe(mode),
 _lazy_supported(), _cannot_reset() -> the exception a reset that has to create an env raises (None: it can; what no reset at all
 can do, SingleSnake's other snake lengths, it raises itself), _start_args()
@@ -773,3 +773,80 @@ class FastStepMixin(object):
         self._done_all_false()  # every done env was reset
         return dict(actions=actions, probs=probs, values=values, rewards=reward, **dict(zip(self._FLAG_KEYS, flags)),
                     observations=obs, state=obs[-1] if T > 0 else state.reshape(shape), status=status)
+
+    # ------------------------------------------------------------------ frames of a fused window (extension)
+
+    def record_start(self, select) -> 'FrameRecord':
+        """Call right before a fused window (`rollout`, `policy_rollout`) whose frames are wanted for the envs `select`
+        (a list or int64 tensor of env indices of this object, any order; an index outside [0, num_envs) is reported by
+        `record_frames` in `status`, not here).  Applies a postponed reset, copies those envs' planes and notes the call
+        counter, seed, env_offset, size and start location the window will run with.  Nothing a later call returns
+        changes: the counter is not consumed and the planes are only read.  What it does besides reading: the postponed
+        reset runs now instead of inside the next launch, and a lazy mirror is written out to `envs` (it stays current)."""
+        sel = torch.as_tensor(select, dtype=torch.long).to(self.device).reshape(-1).contiguous()
+        if sel.numel() == 0:
+            raise RuntimeError('record_start: select is empty')
+        start_args = self._start_args()
+        if self._fs.pending:
+            self._flush()
+        self._write_out()
+        # (not `_state`: a `reset(done)` that follows a step directly keeps the observation that step's launch made for it)
+        envs = self._checked(self._envs)
+        # (the gather itself must stay inside the tensor: what is out of range is the replay kernel's to report)
+        start = envs.index_select(0, sel.clamp(0, self.num_envs - 1))
+        return FrameRecord(self, sel, start, int(self._fs.call), start_args)
+
+    def record_frames(self, rec: 'FrameRecord', actions: torch.Tensor) -> dict:
+        """The frames of the window run right after `rec = env.record_start(select)`: `actions` is `out['actions']` of
+        that `policy_rollout` (any `population=`: indices are the object's) or `rollout` call, (T, num_envs) int64.
+        One launch replays the selected envs from their saved planes (wurm_amd/csrc/rollout_frames.hpp).  Returns
+        `frames` (T + 1, k, 3, S, S) uint8 on the device — frame t is what `_get_rgb()[select]` shows before step t,
+        frame T what the window left behind —, `final` (k, C, S, S): the planes after the window (== env.envs[select]) and
+        `status` (k) uint8: 1 where `select` was outside [0, num_envs) (that env's frames and planes are zeros).
+
+        The rule that ties `rec` to the window: every entry point that draws random numbers takes its counters from
+        `_next_call` — `step` 1, a `reset` (postponed or not) 1, `_create_envs` 1, a window of T steps 2 T (step t uses
+        c + 2 t, its reset c + 2 t + 1).  `record_start` notes the counter c it saw; here the object's counter must be
+        exactly c + 2 T, T = actions.shape[0]: the window, and nothing else that consumed a counter, ran in between
+        — and `record_frames` comes before the next such call.  RuntimeError otherwise, for a `rec` of another object and
+        for actions of another shape, dtype or device, and if `start_location` is no longer the one `record_start` saw.
+        What cannot be seen here, because it consumes no counter: assigning or editing `env.envs` between `record_start`
+        and the window (`final` then differs from `env.envs[select]`).  And `policy_rollout` leaves an env outside its
+        domain untouched (its `status` != 0: not a well-formed snake / not one agent and one food, only ever by hand)
+        while the replay steps whatever planes it was given: for such an env the frames are not what the window did,
+        and again `final` differs from `env.envs[select]` — look at the window's own `status` for the selected envs."""
+        if not isinstance(rec, FrameRecord) or rec.owner() is not self:
+            raise RuntimeError('record_frames: this record was started on another env object')
+        N = self.num_envs
+        if not isinstance(actions, torch.Tensor) or actions.dtype != torch.long or actions.dim() != 2 or \
+                actions.shape[1] != N or actions.device != self.device or not actions.is_contiguous():
+            raise RuntimeError(f'record_frames: actions must be the contiguous int64 (T, {N}) device tensor the window returned')
+        T = int(actions.shape[0])
+        if rec.start_args != tuple(self._start_args()):
+            raise RuntimeError(f'record_frames: stale record — start_location was {rec.start_args} at record_start and is '
+                               f'{tuple(self._start_args())} now')
+        if int(self._fs.call) != rec.call + 2 * T or (rec.seed, rec.env_offset, rec.size) != (
+                int(self.seed), int(self.env_offset), int(self.size)):
+            raise RuntimeError(f'record_frames: stale record — it was started at call counter {rec.call} and a window of '
+                               f'{T} steps ends at {rec.call + 2 * T}, but the counter is {int(self._fs.call)}: another '
+                               f'call that draws random numbers ran since record_start besides the window')
+        k, S, dev = rec.select.numel(), self.size, self.device
+        frames = torch.empty((T + 1, k, 3, S, S), dtype=torch.uint8, device=dev)
+        final = torch.empty((k, self._CHANNELS, S, S), dtype=torch.float32, device=dev)
+        status = torch.empty(k, dtype=torch.uint8, device=dev)
+        rc = _lib.call(dev.index, getattr(_lib.lib(), self._FRAMES_FN), _lib.ptr(rec.start), _lib.ptr(rec.select),
+                       _lib.ptr(actions) if T > 0 else None, _lib.ptr(frames), _lib.ptr(final), _lib.ptr(status),
+                       _lib.i64(k), _lib.i64(N), S, _lib.i64(T), *rec.start_args, _lib.u64(rec.seed), _lib.u64(rec.call),
+                       _lib.i64(rec.env_offset), _lib.stream_ptr(dev.index))
+        _lib.check(rc, self._NAME + '.record_frames')
+        return dict(frames=frames, final=final, status=status)
+
+
+class FrameRecord(object):
+    """What `record_start` keeps of the moment before a window: the selected envs' planes and what keys their random draws."""
+
+    def __init__(self, env, select, start, call, start_args):
+        import weakref
+        self.owner = weakref.ref(env)
+        self.select, self.start, self.call, self.start_args = select, start, call, tuple(start_args)
+        self.seed, self.env_offset, self.size = int(env.seed), int(env.env_offset), int(env.size)

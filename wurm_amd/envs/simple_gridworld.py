@@ -25,6 +25,7 @@ class SimpleGridworld(FastStepMixin):
     _ROLLOUT_FNS = ('wurm_grid_rollout', 'wurm_grid_rollout_resident')
     _POLICY_FN = 'wurm_grid_policy_rollout'
     _POLICY_POP_FN = 'wurm_grid_policy_rollout_pop'
+    _FRAMES_FN = 'wurm_grid_rollout_frames'
     _FLAG_KEYS = ('dones', 'edge_collision')
     _BAD_STATUS = 'some envs do not hold exactly one agent and one food'
     _RESIDENT_FNS = ('wurm_grid_resident_bytes', 'wurm_grid_resident_size', 'wurm_grid_resident_flush')

@@ -40,6 +40,7 @@ class SingleSnake(FastStepMixin):
     _ROLLOUT_FNS = ('wurm_single_rollout', 'wurm_single_rollout_resident')
     _POLICY_FN = 'wurm_single_policy_rollout_mode'
     _POLICY_POP_FN = 'wurm_single_policy_rollout_pop'
+    _FRAMES_FN = 'wurm_single_rollout_frames'
     _FLAG_KEYS = ('dones', 'self_collision', 'edge_collision')
     _BAD_STATUS = 'some envs are not well-formed snakes'
     _EMPTY_ROLLOUT_SKIPS_MIRROR = True   # rollout(): no steps, no look at the mirror (9 x 9's is not the rollout's anyway)

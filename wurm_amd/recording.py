@@ -31,6 +31,18 @@ class VideoRecorder(object):
             raise RuntimeError(f'render(mode="rgb_array") returned shape {frame.shape}, expected (H, W, 3)')
         self.frames.append(frame.astype(np.uint8))
 
+    def capture_frames(self, array):
+        """Appends many finished (H, W, 3) frames at once, in order: a (T, H, W, 3) array or a sequence of frames, e.g.
+        `wurm_amd._render.tile_frames(env.record_frames(rec, actions)['frames'], env.render_args)` for a fused window
+        (the env is not asked to render)."""
+        if not self.enabled or self.closed:
+            return
+        for frame in array:
+            frame = np.asarray(frame)
+            if frame.ndim != 3 or frame.shape[-1] != 3:
+                raise RuntimeError(f'capture_frames: a frame of shape {frame.shape}, expected (H, W, 3)')
+            self.frames.append(frame.astype(np.uint8))
+
     def close(self):
         """Writes the file (nothing if no frame was captured) and releases the frames."""
         if self.closed:
@@ -76,3 +88,51 @@ class VideoRecorder(object):
             self.close()
         except Exception:
             pass
+
+
+class WindowRecorder(object):
+    """Video of chosen envs of a loop of FUSED windows (examples/a2c_fused_learner.py, a2c_pbt.py: `--save-video`), which
+    never materialise the states between their steps: every `interval`-th window is replayed for the envs `select` after
+    the fact (`env.record_start` / `env.record_frames`, one launch and one device-to-host copy per recorded window) and its
+    frames are tiled row-major into a near-square picture.  A window that is not recorded costs one integer comparison.
+    Of two recorded windows in a row the second one's first frame is dropped (it is the first one's last): this assumes
+    that nothing but the windows touches the env between them, as in the examples' loops.
+
+        rec = recorder.start(window)                 # in front of env.policy_rollout / env.rollout
+        out = env.policy_rollout(...)
+        recorder.finish(rec, out['actions'])         # before the next call on the env; nothing to do if rec is None
+        recorder.close()                             # writes the file (VideoRecorder: .mp4 / .npy / GIF)
+    """
+
+    def __init__(self, env, path: str, select, interval: int = 1, tile_pixels: int = 128, frames_per_sec: int = 12):
+        self.env, self.select, self.interval = env, [int(i) for i in select], max(1, int(interval))
+        k = len(self.select)
+        cols = int(np.ceil(np.sqrt(k)))
+        self.render_args = {'num_rows': -(-k // cols), 'num_cols': cols, 'size': int(tile_pixels)}
+        self.video = VideoRecorder(None, path, frames_per_sec=frames_per_sec)
+        self._window, self._last = None, None
+
+    def start(self, window: int):
+        """the record of window number `window` (0, 1, ...), or None if it is not one of every `interval`-th"""
+        if window % self.interval != 0:
+            return None
+        self._window = window
+        return self.env.record_start(self.select)
+
+    def finish(self, rec, actions):
+        if rec is None:
+            return
+        from wurm_amd._render import tile_frames
+        frames = self.env.record_frames(rec, actions)['frames']
+        if self._last is not None and self._window == self._last + 1:
+            frames = frames[1:]          # (the state a window leaves behind is the first frame of the one that follows)
+        self._last = self._window
+        frames = frames.cpu().numpy()
+        tiles = self.render_args['num_rows'] * self.render_args['num_cols']
+        if tiles > frames.shape[1]:      # (the last row of tiles is not full: black tiles)
+            pad = np.zeros((frames.shape[0], tiles - frames.shape[1]) + frames.shape[2:], np.uint8)
+            frames = np.concatenate([frames, pad], axis=1)
+        self.video.capture_frames(tile_frames(frames, self.render_args))
+
+    def close(self):
+        self.video.close()

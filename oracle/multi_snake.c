@@ -594,11 +594,13 @@ int oracle_multi_check(const float *foods, const float *heads, const float *bodi
                 if (sum != 0.0f) m |= MCHK_DEAD_NONZERO;
                 continue;
             }
-            float hs = 0, bs = 0, bm = bd[0], hb = 0, hf = 0;
+            /* :742 snake_consistency(living_envs.round()): every plane rounded half to even, like torch.round */
+            float hs = 0, bs = 0, bm = nearbyintf(bd[0]), hb = 0, hf = 0;
             for (int c = 0; c < C; ++c) {
-                if (!(food[c] == 0.0f || food[c] == 1.0f)) m |= 1;
-                hs += hd[c]; bs += bd[c]; hb += hd[c] * bd[c]; hf += hd[c] * food[c];
-                if (bd[c] > bm) bm = bd[c];
+                const float f = nearbyintf(food[c]), h = nearbyintf(hd[c]), b = nearbyintf(bd[c]);
+                if (!(f == 0.0f || f == 1.0f)) m |= 1;
+                hs += h; bs += b; hb += h * b; hf += h * f;
+                if (b > bm) bm = b;
             }
             if (hs != 1.0f) m |= 2;
             if (!(bs > 0.0f)) m |= 4;

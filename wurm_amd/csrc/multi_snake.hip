@@ -1434,7 +1434,7 @@ __global__ __launch_bounds__(256) void multi_check_kernel(MultiArgs p)
     for (int k = 0; k < cpl; ++k) {
         int c = lane + 64 * k;
         if (c < C) {
-            const float f = foodp[c];
+            const float f = rintf(foodp[c]); // the reference checks living_envs.round() (:742): 0.5 is a 0, 1.5 a 2
             badf |= !(f == 0.0f || f == 1.0f);
             cnt[c] = 0;
         }

@@ -80,6 +80,11 @@ int64_t wurm_launch_count(void);
  * Diagnostic only (bench.py and tests/test_dispatch_table.py name a launch by it); a static string. */
 const char *wurm_single_last_route(void);
 
+/* Waves per env of that launch: 2 if it was rollout_s9_kernel's pair form ("rollout_s9" / "rollout_s9_injected" with at most
+ * WURM_S9_PAIR_MAX_ENVS envs, default 1024: a workgroup of a stepping wave and a helper wave per env; 0 = never), else 1.
+ * Results do not depend on the form.  Diagnostic only (tests/test_s9_pair_rollout.py tells the two forms apart by it). */
+int wurm_single_last_waves_per_env(void);
+
 /* The same for MultiSnake: the kernel instantiation that served the calling thread's last wurm_multi_* launch, by its row in
  * the list in wurm_amd/csrc/multi_snake.hip ("step_rng_full_k4_s25", "rollout_two_rng", "rollout_group_8215_rng", "reset_wg",
  * ...; "none" before the first), followed by how it was driven where one kernel is driven in several ways: "+emit_wave" /

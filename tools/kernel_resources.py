@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel resource table from the compiler's own remarks (-Rpass-analysis=kernel-resource-usage): VGPRs, AGPRs,
-SGPRs, spills, scratch, LDS, occupancy (waves per SIMD).  No GPU needed.  usage: tools/kernel_resources.py > profiles/rNN_kernel_resources.txt"""
+SGPRs, spills, scratch, LDS, occupancy (waves per SIMD).  No GPU needed.  usage: tools/kernel_resources.py [unit.hip ...] > profiles/rNN_kernel_resources.txt
+(no unit named: every wurm_amd/csrc/*.hip)"""
 import os
 import re
 import subprocess
@@ -10,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'wurm_amd', 'csrc')
 FLAGS = '-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Rpass-analysis=kernel-resource-usage'.split()
 rows = []
-for src in sorted(f for f in os.listdir(CSRC) if f.endswith('.hip')):
+for src in sorted(sys.argv[1:] or [f for f in os.listdir(CSRC) if f.endswith('.hip')]):
     r = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', *FLAGS, '-c', src, '-o', '/dev/null'],
                        cwd=CSRC, capture_output=True, text=True)
     cur = None

@@ -5,26 +5,78 @@ Needs the instrumented build of the library (s_memtime stamps, wurm_amd/csrc/wur
     make -C wurm_amd/csrc timeline          # -> wurm_amd/libwurm_hip_timeline.so (cross-compiles without a GPU)
     WURM_HIP_LIBRARY=$PWD/wurm_amd/libwurm_hip_timeline.so python tools/kernel_timeline.py [--kernel resident|lane_step]
                                                             [--envs 65536] [--epw 32] [--form ref|noobs]
+    ... python tools/kernel_timeline.py --kernel s9 [--envs 512] [--steps 1024] [--pair 0|1]
 Every wave overwrites the first 64 bytes of its own observation block with eight stamps once its stores have drained; this
 script reads them back from the observation `step` returned and prints, per segment between two stamps, the distribution
 over the waves in s_memtime ticks — counters of different XCDs are not synchronised, so only differences within one wave
-are used.  The observations of a timeline run are garbage by construction."""
+are used.  The observations of a timeline run are garbage by construction.
+
+--kernel s9: the stepping wave of rollout_s9_kernel (the headline rollout, --envs x 9 x 9 'partial_2', --steps batch-steps per
+launch), one wave form (--pair 0) or pair form (--pair 1).  Its stamps are TOTALS over the launch's 64-step chunks."""
 import argparse
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap = argparse.ArgumentParser()
-ap.add_argument('--kernel', default='resident', choices=['resident', 'lane_step', 'grid'])
+ap.add_argument('--kernel', default='resident', choices=['resident', 'lane_step', 'grid', 's9'])
 ap.add_argument('--size', type=int, default=36, help='--kernel grid: the grid size (cfg5: 8192 envs of 36 x 36, default observation)')
-ap.add_argument('--envs', type=int, default=65536)
+ap.add_argument('--envs', type=int, default=None, help='default 65536; --kernel s9: 512')
 ap.add_argument('--epw', type=int, default=0)
 ap.add_argument('--form', default='ref', choices=['ref', 'noobs'])
 ap.add_argument('--iters', type=int, default=12)
+ap.add_argument('--steps', type=int, default=1024, help='--kernel s9: batch-steps per launch')
+ap.add_argument('--pair', type=int, default=0, choices=[0, 1], help='--kernel s9: the pair form (two waves per env)')
 args = ap.parse_args()
 if 'timeline' not in os.environ.get('WURM_HIP_LIBRARY', ''):
     sys.exit('set WURM_HIP_LIBRARY to the instrumented library (see the docstring)')
-N = args.envs
+N = args.envs if args.envs is not None else (512 if args.kernel == 's9' else 65536)
+
+
+def s9_timeline():
+    """slots of rollout_s9_kernel's stepper (single_kernels.hpp): 0 entry, 7 end (stores drained); totals over the chunks:
+    5 state load + setup, 1 wait for the chunk's inputs (one wave: the tape load, which also drains the previous chunk's
+    observation stores; pair: the barrier and the LDS reads), 2 prologue arithmetic (one wave only), 3 step loop, 4 flush
+    (one wave: the record stores issued; pair: the record's LDS write and the barrier)"""
+    import numpy as np
+    import torch
+    from wurm_amd import _lib
+    from wurm_amd.envs import SingleSnake
+    N_ = N
+    T = args.steps
+    env = SingleSnake(num_envs=N_, size=9, observation_mode='partial_2', device='cuda', seed=0)
+    _lib.set_option('WURM_S9_PAIR_MAX_ENVS', (1 << 40) if args.pair else 0)
+    g = torch.Generator(device='cuda').manual_seed(1)
+    rows = []
+    for it in range(args.iters):
+        out = env.rollout(torch.randint(0, 4, (T, N_), device='cuda', generator=g))
+        torch.cuda.synchronize()
+        assert _lib.lib().wurm_single_last_waves_per_env() == 1 + args.pair
+        obs = out['observations']
+        if it >= 4:
+            rows.append(obs[0].reshape(N_, -1)[:, :16].contiguous().view(torch.int64).cpu().numpy().astype(np.int64))
+    st = np.concatenate(rows)
+    life = st[:, 7] - st[:, 0]
+    st, life = st[(life > 0) & (life < 10 ** 9)], life[(life > 0) & (life < 10 ** 9)]
+    print(f'rollout_s9_kernel, {N_} envs x {T} steps, {"pair" if args.pair else "one-wave"} form: {len(life)} stepper samples; '
+          f's_memtime ticks, totals over {(T + 63) // 64} chunks')
+    named = [(5, 'state load + setup'), (1, 'wait for the chunk inputs'), (2, 'prologue arithmetic'), (3, 'step loop'),
+             (4, 'flush / hand-over')]
+    for k, name in named:
+        c = st[:, k]
+        print(f'  {name:>26s} p10 {int(np.percentile(c, 10)):7d}  p50 {int(np.median(c)):7d}  p90 {int(np.percentile(c, 90)):7d}  '
+              f'max {int(c.max()):7d}   {100.0 * np.median(c) / np.median(life):5.1f} % of p50 life')
+    rest = life - sum(st[:, k] for k, _ in named)
+    print(f'  {"state store + drain":>26s} p10 {int(np.percentile(rest, 10)):7d}  p50 {int(np.median(rest)):7d}  '
+          f'p90 {int(np.percentile(rest, 90)):7d}  max {int(rest.max()):7d}   {100.0 * np.median(rest) / np.median(life):5.1f} % of p50 life')
+    print(f'  wave lifetime: p10 {int(np.percentile(life, 10))}  p50 {int(np.median(life))}  p90 {int(np.percentile(life, 90))}  max {int(life.max())}')
+    per_chunk = 100.0 * np.median(st[:, 1] + st[:, 2] + st[:, 4]) / np.median(life)
+    print(f'  per-chunk work around the step loop (wait + prologue + flush): {per_chunk:.1f} % of p50 life')
+
+
+if args.kernel == 's9':
+    s9_timeline()
+    sys.exit(0)
 if args.kernel == 'grid':
     os.environ['WURM_GRID_STEP_MIN_CELLS'] = '0'
     names = ['entry', 'grid in LDS', 'action', 'stepped', 'outputs', 'obs issued', 'state stored', 'drained']

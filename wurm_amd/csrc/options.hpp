@@ -24,6 +24,7 @@ struct Options {
     long long gridworld_lane_epw;    // WURM_GRIDWORLD_LANE_EPW    SimpleGridworld lane rollout, image modes: envs per wave (4..64; -1 = by batch size)
     long long grid_rollout_min_size; // WURM_GRID_ROLLOUT_MIN_SIZE SingleSnake rollouts on LDS clock grids from this grid size on (-1 = by observation mode: 14 / 18 / 26; 12 = every size they serve)
     long long policy_wide;           // WURM_POLICY_WIDE           1 = fused actor on policy_wide_kernel even where policy_rollout.hpp's kernels serve (S <= 11, n <= 3)
+    long long s9_pair_max_envs;      // WURM_S9_PAIR_MAX_ENVS      9 x 9 rollouts of small batches (rollout_s9_kernel): two waves per env, stepper and helper, up to this many envs (1024; 0 = always one wave per env)
 };
 
 extern Options opt;

@@ -344,7 +344,9 @@ __device__ __forceinline__ bool small_step(Env<2> &e, const Geo &g, float *__res
 
 // One transition of one env held in registers.  WRITE: changed cells are written through to HBM as they are
 // produced (per-call kernels); !WRITE: registers only (rollout kernel).
-template <int CPL, bool SNAKE, bool WRITE>
+// HEADS (grids of at most 128 cells; rollout_s9_kernel's generic path sets it): a 0 / 1 head plane with SEVERAL heads moves as
+// the reference's does, every head of it.
+template <int CPL, bool SNAKE, bool WRITE, bool HEADS = false>
 __device__ __forceinline__ void step_core(Env<CPL> &e, const Geo &g, float *__restrict__ envp, long long a_in,
                                           StepOut &out, u64 seed, u64 call, u64 env_id, bool use_inject,
                                           int inject_cell, signed char *lds)
@@ -369,65 +371,153 @@ __device__ __forceinline__ void step_core(Env<CPL> &e, const Geo &g, float *__re
     }
     const int ai = (int)(((a % 4) + 4) % 4);
 
-    // head shift (single_snake.py:225-233 / simple_gridworld.py:149-157): by -TAP[a]; off-grid => vanishes
-    const int headcell = find_head<CPL>(e);
-    int newhead = -1, ny = -1, nx = -1;
-    if (headcell >= 0) {
-        int hy = div_size(headcell, g.rcpS), hx = headcell - hy * S;
-        ny = hy - tap_y(ai);
-        nx = hx - tap_x(ai);
-        if (ny >= 0 && ny < S && nx >= 0 && nx < S) newhead = ny * S + nx;
-    }
+    // Two spellings of the same transition.  HEADS: EVERY head of the head plane moves, as in the reference (a state edited
+    // by hand: the library itself produces at most one head).  Otherwise the one-head form; several heads are outside its
+    // domain (deviations).
+    if constexpr (HEADS && CPL <= 2) {
+        // head shift (single_snake.py:225-233 / simple_gridworld.py:149-157): the whole channel moves by -TAP[a]; what leaves
+        // the grid vanishes.  newbits: bit k = cell lane + 64 k holds a head after the move.  The states the library itself
+        // produces have at most one head, and that one is moved as a scalar; several heads (a state edited by hand) move
+        // through LDS, one byte per cell, each cell looking at the cell its head would come from.
+        const bool many = popc64(ballot(e.head != 0)) > 1 || ballot((e.head & (e.head - 1)) != 0) != 0;
+        int newhead = -1, ny = -1, nx = -1;
+        u64 newbits = 0;
+        if (!many) {
+            const int headcell = find_head<CPL>(e);
+            if (headcell >= 0) {
+                int hy = div_size(headcell, g.rcpS), hx = headcell - hy * S;
+                ny = hy - tap_y(ai);
+                nx = hx - tap_x(ai);
+                if (ny >= 0 && ny < S && nx >= 0 && nx < S) newhead = ny * S + nx;
+            }
+    #pragma unroll
+            for (int k = 0; k < CPL; ++k)
+                if (lane + 64 * k == newhead) newbits |= 1ull << k;
+        } else {
+            wave_lds_sync();
+    #pragma unroll 1
+            for (int k = 0; k < CPL; ++k)
+                if ((g.valid >> k) & 1) lds[lane + 64 * k] = (signed char)((e.head >> k) & 1);
+            wave_lds_sync();
+    #pragma unroll 1
+            for (int k = 0; k < CPL; ++k) {
+                if (!((g.valid >> k) & 1)) continue;
+                const int c = lane + 64 * k, y = div_size(c, g.rcpS), x = c - y * S;
+                const int fy = y + tap_y(ai), fx = x + tap_x(ai);
+                if (fy >= 0 && fy < S && fx >= 0 && fx < S && lds[fy * S + fx] != 0) newbits |= 1ull << k;
+            }
+            wave_lds_sync();
+            newhead = first_cell(newbits, lane); // the first head in row-major order: what a crop is centred on
+        }
 
-    bool eat_l = false;
-#pragma unroll
-    for (int k = 0; k < CPL; ++k) eat_l |= (lane + 64 * k == newhead) && ((e.food >> k) & 1);
-    const bool EAT = ballot(eat_l) != 0; // single_snake.py:242 head_food_overlap
+        // single_snake.py:242 head_food_overlap: the number of heads that moved onto food
+        const int overlap = many ? wave_sum_i32(__popcll(newbits & e.food)) : (int)(ballot((newbits & e.food) != 0) != 0);
+        const bool EAT = overlap != 0;
 
-    bool selfc_l = false;
-    u64 newbits = 0;
-#pragma unroll
-    for (int k = 0; k < CPL; ++k) {
-        const int c = lane + 64 * k;
-        const bool is_new = (c == newhead);
-        if (SNAKE) {
-            const int b0 = e.body[k];
-            int b = b0;
-            if (!EAT) b = max(b - 1, 0); // :246-249 decay unless food was eaten
+        bool selfc_l = false;
+    #pragma unroll
+        for (int k = 0; k < CPL; ++k) {
+            const int c = lane + 64 * k;
+            const bool is_new = (newbits >> k) & 1;
+            if (SNAKE) {
+                const int b0 = e.body[k];
+                int b = b0;
+                if (!EAT) b = max(b - 1, 0); // :246-249 decay unless food was eaten
+                if (is_new) {
+                    selfc_l |= b > 0;        // :252 self collision (after the decay)
+                    b += L + overlap;        // :258-262 new head segment
+                }
+                if (WRITE && b != b0) envp[2 * C + c] = (float)b;
+                e.body[k] = b;
+            }
             if (is_new) {
-                selfc_l |= b > 0;        // :252 self collision (after the decay)
-                b += L + (EAT ? 1 : 0);  // :258-262 new head segment
+                if ((e.food >> k) & 1) {     // :270-272 food removal
+                    e.food &= ~(1ull << k);
+                    if (WRITE) envp[c] = 0.0f;
+                }
             }
-            if (WRITE && b != b0) envp[2 * C + c] = (float)b;
-            e.body[k] = b;
+            if (WRITE && (((e.head >> k) & 1) != (u64)is_new)) envp[C + c] = is_new ? 1.0f : 0.0f;
         }
-        if (is_new) {
-            newbits |= 1ull << k;
-            if ((e.food >> k) & 1) {     // :270-272 food removal
-                e.food &= ~(1ull << k);
-                if (WRITE) envp[c] = 0.0f;
+        e.head = newbits;
+        const bool SELFC = SNAKE && (ballot(selfc_l) != 0);
+
+        if (EAT) { // :277-282
+            u32 word = 0;
+            if (!use_inject) word = rng_words(seed, call, env_id, RNG_FOOD, 0).w[0];
+            add_food<CPL, SNAKE, WRITE>(e, g, envp, use_inject, inject_cell, word);
+        }
+
+        // :290-295 edge collision: head not in the interior (on the border ring or gone)
+        const bool EDGEC = many ? ballot((newbits & g.interior) != 0) == 0
+                                : !(newhead >= 0 && ny >= 1 && ny <= S - 2 && nx >= 1 && nx <= S - 2);
+
+        out.action = a;
+        out.headcell = newhead;
+        out.reward = (float)overlap;
+        out.selfc = SELFC;
+        out.edgec = EDGEC;
+        out.done = SELFC | EDGEC;
+    } else {
+        // head shift (single_snake.py:225-233 / simple_gridworld.py:149-157): by -TAP[a]; off-grid => vanishes
+        const int headcell = find_head<CPL>(e);
+        int newhead = -1, ny = -1, nx = -1;
+        if (headcell >= 0) {
+            int hy = div_size(headcell, g.rcpS), hx = headcell - hy * S;
+            ny = hy - tap_y(ai);
+            nx = hx - tap_x(ai);
+            if (ny >= 0 && ny < S && nx >= 0 && nx < S) newhead = ny * S + nx;
+        }
+
+        bool eat_l = false;
+    #pragma unroll
+        for (int k = 0; k < CPL; ++k) eat_l |= (lane + 64 * k == newhead) && ((e.food >> k) & 1);
+        const bool EAT = ballot(eat_l) != 0; // single_snake.py:242 head_food_overlap
+
+        bool selfc_l = false;
+        u64 newbits = 0;
+    #pragma unroll
+        for (int k = 0; k < CPL; ++k) {
+            const int c = lane + 64 * k;
+            const bool is_new = (c == newhead);
+            if (SNAKE) {
+                const int b0 = e.body[k];
+                int b = b0;
+                if (!EAT) b = max(b - 1, 0); // :246-249 decay unless food was eaten
+                if (is_new) {
+                    selfc_l |= b > 0;        // :252 self collision (after the decay)
+                    b += L + (EAT ? 1 : 0);  // :258-262 new head segment
+                }
+                if (WRITE && b != b0) envp[2 * C + c] = (float)b;
+                e.body[k] = b;
             }
+            if (is_new) {
+                newbits |= 1ull << k;
+                if ((e.food >> k) & 1) {     // :270-272 food removal
+                    e.food &= ~(1ull << k);
+                    if (WRITE) envp[c] = 0.0f;
+                }
+            }
+            if (WRITE && (((e.head >> k) & 1) != (u64)is_new)) envp[C + c] = is_new ? 1.0f : 0.0f;
         }
-        if (WRITE && (((e.head >> k) & 1) != (u64)is_new)) envp[C + c] = is_new ? 1.0f : 0.0f;
+        e.head = newbits;
+        const bool SELFC = SNAKE && (ballot(selfc_l) != 0);
+
+        if (EAT) { // :277-282
+            u32 word = 0;
+            if (!use_inject) word = rng_words(seed, call, env_id, RNG_FOOD, 0).w[0];
+            add_food<CPL, SNAKE, WRITE>(e, g, envp, use_inject, inject_cell, word);
+        }
+
+        // :290-295 edge collision: head not in the interior (on the border ring or gone)
+        const bool EDGEC = !(newhead >= 0 && ny >= 1 && ny <= S - 2 && nx >= 1 && nx <= S - 2);
+
+        out.action = a;
+        out.headcell = newhead;
+        out.reward = EAT ? 1.0f : 0.0f;
+        out.selfc = SELFC;
+        out.edgec = EDGEC;
+        out.done = SELFC | EDGEC;
     }
-    e.head = newbits;
-    const bool SELFC = SNAKE && (ballot(selfc_l) != 0);
-
-    if (EAT) { // :277-282
-        u32 word = 0;
-        if (!use_inject) word = rng_words(seed, call, env_id, RNG_FOOD, 0).w[0];
-        add_food<CPL, SNAKE, WRITE>(e, g, envp, use_inject, inject_cell, word);
-    }
-
-    // :290-295 edge collision: head not in the interior (on the border ring or gone)
-    const bool EDGEC = !(newhead >= 0 && ny >= 1 && ny <= S - 2 && nx >= 1 && nx <= S - 2);
-
-    out.action = a;
-    out.headcell = newhead;
-    out.reward = EAT ? 1.0f : 0.0f;
-    out.selfc = SELFC;
-    out.edgec = EDGEC;
-    out.done = SELFC | EDGEC;
 }
 
 // ------------------------------------------------------------------------------------------------ reset
@@ -858,7 +948,7 @@ __device__ __forceinline__ void fast_partial_small(const Env<CPL> &e, const Geo 
 // OBSK >= 0 fixes the observation mode at compile time and INJ = false compiles the injection plumbing out: the
 // flagship configuration (9x9, partial_n / no observation, RNG mode) gets a lean instantiation, everything else the
 // fully general one (OBSK = -1, INJ = true).
-template <int CPL, bool SNAKE, int OBSK, bool INJ>
+template <int CPL, bool SNAKE, int OBSK, bool INJ, bool HEADS = false>
 __device__ __forceinline__ void rollout_generic(const StepArgs &p, long long env, float *__restrict__ envp, const Geo &g,
                                                 Env<CPL> &e, signed char *lds)
 {
@@ -903,7 +993,7 @@ __device__ __forceinline__ void rollout_generic(const StepArgs &p, long long env
                                     inj_r ? p.inject_reset + ((t0 + j) * p.N + env) * 4 : nullptr);
             } else {
                 const long long a_in = lane_value64(my_a, j);
-                step_core<CPL, SNAKE, false>(e, g, nullptr, a_in, out, p.seed, call, env_id, inj_f, inj_cell, lds);
+                step_core<CPL, SNAKE, false, HEADS>(e, g, nullptr, a_in, out, p.seed, call, env_id, inj_f, inj_cell, lds);
                 if (obs_mode != WURM_OBS_NONE)
                     write_obs<CPL, SNAKE>(e, g, out.headcell, obs_t, obs_mode, p.obs_n, lds);
                 if (out.done) {
@@ -1010,6 +1100,22 @@ __device__ __forceinline__ S9Reset s9_reset_draw(u64 seed, u64 call, u64 env_id)
     r.a = d | (((qy + 1) * 8 + qx + 1) << 2);
     r.b = (sc + dc) | (sc << 7) | ((sc - dc) << 14);
     return r;
+}
+
+// what the 64 steps of a chunk need that does not depend on the state, lane j holding step t0 + j's (rollout_s9_kernel)
+struct S9Chunk {
+    int mov01, mov23; // the move entries for the orientations 0, 1 and 2, 3
+    S9Reset reset;    // the would-be reset
+    int food;         // RNG: the word the food cell of an eating step is drawn with; injected: its code (-1: none)
+};
+
+// Barrier between the two waves of rollout_s9_kernel's pair form.  It orders LDS only: the waves' global stores stay in
+// flight across it (__syncthreads() would wait for vmcnt(0), that is for every observation store of the chunk).
+__device__ __forceinline__ void pair_barrier()
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
 }
 
 // v = value in the lanes of `lanes`, unchanged elsewhere — with the lane mask taken from an SGPR pair as it is (the

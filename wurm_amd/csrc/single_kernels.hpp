@@ -353,16 +353,120 @@ __global__ __launch_bounds__(256) void rollout_lean_kernel(StepArgs p)
 // INJ: the random outcomes (food cell of an eating step, seed cell / direction / food cell of a reset) come from
 // p.inject_food / p.inject_reset instead of Philox, so that the tapes recorded from the reference (tests/golden) run
 // through THIS kernel; the RNG instantiation is compiled without any of it.
-template <int OBSK, bool INJ = false>
+// PAIR: a workgroup of two waves per env (single_launch.hpp: batches of at most WURM_S9_PAIR_MAX_ENVS envs).  Wave 1 does
+// what a chunk needs around its step loop — tape load, move entries, Philox blocks or recorded outcomes one chunk ahead,
+// the record stores one chunk behind — and wave 0 only steps (DESIGN.md section 4 has the protocol and the measurements).
+template <int OBSK, bool INJ = false, bool PAIR = false>
 __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
 {
     constexpr int CPL = 2, S = 9;
     static_assert(OBSK == WURM_OBS_PARTIAL || OBSK == WURM_OBS_NONE, "9x9 rollout: partial_n or no observation");
     const int wave = uniform((int)(threadIdx.x >> 6)), wpb = (int)(blockDim.x >> 6);
-    const long long env = xcd_block(blockIdx.x, gridDim.x) * wpb + wave;
+    // PAIR: one workgroup of two waves per env; both take the next line's exit, or neither
+    const long long env = PAIR ? xcd_block(blockIdx.x, gridDim.x) : xcd_block(blockIdx.x, gridDim.x) * wpb + wave;
     if (env >= p.N) return;
     const Geo g = make_geo<CPL>(S);
     const int lane = g.lane;
+    const u64 env_id = (u64)(p.env_offset + env);
+    WURM_TL_DECL;
+    WURM_TL(0);
+    WURM_TL(6);
+
+    // What the 64 steps of the chunk at t0 need that does not depend on the state, step t0 + lane in lane `lane`.
+    const auto chunk_draw = [&](const long long t0, const int nt) __attribute__((always_inline)) {
+        S9Chunk ch;
+        const long long my_t = t0 + lane;
+        long long my_a = lane < nt ? load_action(p.actions, p.act_dtype, my_t * p.N + env) : 0;
+        asm volatile("" : "+v"(my_a)); // retire the load here, not in front of the first readlane of the step loop
+        if constexpr (!PAIR) WURM_TL_LAP(1);
+        // Moves of step t0 + lane for each of the four orientations the snake may have by then, 16 bits each:
+        // next orientation << 4 | (code step & 63) << 6 | (sanitised action (single_snake.py:221-222) & 7) << 12, the
+        // step being -TAP[action] (:225-233); bits 0-3 are zero, so the low 6 bits of an entry are the shift that picks
+        // the NEXT step's entry.  The step loop reads both words with readlanes that do not depend on the state.
+        {
+            const auto entry = [](int a_out) {
+                const int ai = a_out & 3;
+                return ((ai ^ 2) << 4) | (((-tap_y(ai) * 8 - tap_x(ai)) & 63) << 6) | ((a_out & 7) << 12);
+            };
+            const bool in_range = my_a >= 0 && my_a < 4;
+            const int a_small = in_range ? (int)my_a : 7, a_mod = (int)(my_a % 4);
+            int me[4];
+#pragma unroll
+            for (int o = 0; o < 4; ++o)
+                me[o] = entry(o == a_small ? (o ^ 2) : a_mod);
+            ch.mov01 = me[0] | (me[1] << 16);
+            ch.mov23 = me[2] | (me[3] << 16);
+        }
+        const u64 my_call = p.call + 2ull * (u64)my_t; // step t uses call0 + 2t, its reset call0 + 2t + 1
+        if constexpr (INJ) {
+            // recorded outcomes of step t0 + lane, converted to cell codes 8 * row + column (reset_core's layout of inj[])
+            int sy = 4, sx = 4, d = 0, fc = -1, fe = -1;
+            if (lane < nt) {
+                const int *ir = p.inject_reset + (my_t * p.N + env) * 4;
+                sy = ir[0]; sx = ir[1]; d = ir[2]; fc = ir[3];
+                fe = p.inject_food[my_t * p.N + env];
+            }
+            asm volatile("" : "+v"(sy), "+v"(sx), "+v"(d), "+v"(fc), "+v"(fe)); // retire the loads before the step loop
+            d &= 3;
+            const int sc = sy * 8 + sx, dc = tap_y(d) * 8 + tap_x(d);
+            const int fcy = div_size(max(fc, 0), g.rcpS), fey = div_size(max(fe, 0), g.rcpS);
+            const int fcode = (fc >= 0 && fc < S * S) ? fcy * 8 + (fc - fcy * S) : -1;
+            ch.reset.a = d | (fcode << 2);
+            ch.reset.b = (sc + dc) | (sc << 7) | ((sc - dc) << 14);
+            ch.food = (fe >= 0 && fe < S * S) ? fey * 8 + (fe - fey * S) : -1;
+        } else {
+            ch.reset = s9_reset_draw(p.seed, my_call + 1ull, env_id);
+            ch.food = (int)rng_words(p.seed, my_call, env_id, RNG_FOOD, 0).w[0];
+        }
+        return ch;
+    };
+    // The step records of the chunk at t0, lane j's being step t0 + j's: sanitised action, ate, self collision | edge collision << 1
+    const auto flush = [&](const long long t0, const int nt, const int act, const int ate, const int fl) __attribute__((always_inline)) {
+        if (lane < nt) {
+            const long long i = (t0 + lane) * p.N + env;
+            store_action(p.actions, p.act_dtype, i, (long long)act);
+            p.reward[i] = ate ? 1.0f : 0.0f;
+            p.done[i] = (uint8_t)(fl != 0);
+            p.selfc[i] = (uint8_t)(fl & 1);
+            p.edgec[i] = (uint8_t)(fl >> 1);
+        }
+    };
+
+    // PAIR: the helper wave (wave 1) works one chunk ahead of the stepper (wave 0) and one behind it, through LDS behind
+    // rollout_generic's region: chunk buffers k & 1 (S9Chunk, 5 dwords x 64 lanes), record buffers k & 1 (64 dwords: action
+    // & 7 | ate << 3 | collisions << 4), and the stepper's verdict on the state.  Both waves pass 1 + ceil(T / 64) barriers:
+    // B0 once chunk 0 and the verdict are written, B(k+1) at the end of chunk k.  Between B(k) and B(k+1) the helper writes
+    // chunk buffer (k+1) & 1 and reads record buffer (k-1) & 1, the stepper reads chunk buffer k & 1 (at once, into
+    // registers) and writes record buffer k & 1 (last).
+    int *const pair_lds = (int *)(wurm_lds + p.lds_per_wave);
+    constexpr int PAIR_CHUNK = 5 * 64, PAIR_REC = 2 * PAIR_CHUNK, PAIR_LEAN = PAIR_REC + 2 * 64;
+    const long long n_chunks = (p.T + 63) >> 6;
+    if constexpr (PAIR) {
+        if (wave != 0) {
+            const auto draw_into = [&](const long long k) __attribute__((always_inline)) {
+                const long long t0 = k << 6;
+                const S9Chunk ch = chunk_draw(t0, (int)min((long long)64, p.T - t0));
+                int *cb = pair_lds + (int)(k & 1) * PAIR_CHUNK + lane;
+                cb[0] = ch.mov01; cb[64] = ch.mov23; cb[128] = ch.reset.a; cb[192] = ch.reset.b; cb[256] = ch.food;
+            };
+            const auto flush_from = [&](const long long k) __attribute__((always_inline)) {
+                const long long t0 = k << 6;
+                const int rec = pair_lds[PAIR_REC + (int)(k & 1) * 64 + lane];
+                flush(t0, (int)min((long long)64, p.T - t0), (rec << 29) >> 29, (rec >> 3) & 1, rec >> 4);
+            };
+            if (n_chunks > 0) draw_into(0);
+            pair_barrier(); // B0
+            if (uniform(pair_lds[PAIR_LEAN]) == 0) return; // the stepper runs rollout_generic, which has no barrier
+            for (long long k = 0; k < n_chunks; ++k) {
+                if (k + 1 < n_chunks) draw_into(k + 1); // (reads the tape of chunk k + 1 before chunk k - 1 is written back)
+                if (k > 0) flush_from(k - 1);
+                pair_barrier(); // B(k+1)
+            }
+            if (n_chunks > 0) flush_from(n_chunks - 1);
+            return;
+        }
+    }
+
     float *envp = p.envs + env * 3 * (S * S);
     Env<CPL> e;
     load_state<CPL, true>(envp, g, e);
@@ -378,12 +482,15 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
         const bool ring_body = lane_mask((e.body[0] > 0 && !(g.interior & 1)) || (e.body[1] > 0 && !(g.interior & 2))) != 0;
         lean = head_in && food_in && under_food == 0 && !ring_body;
     }
+    if constexpr (PAIR) {
+        if (lane == 0) pair_lds[PAIR_LEAN] = lean ? 1 : 0;
+        pair_barrier(); // B0
+    }
     if (!uniform((int)lean)) {
-        rollout_generic<CPL, true, OBSK, INJ>(p, env, envp, g, e, wurm_lds + wave * p.lds_per_wave);
+        rollout_generic<CPL, true, OBSK, INJ, true>(p, env, envp, g, e, wurm_lds + wave * p.lds_per_wave); // (several heads: as the reference)
         return;
     }
 
-    const u64 env_id = (u64)(p.env_offset + env);
     // code layout: lane = 8 * row + column holds that cell if it is inside the ring
     const int ly = lane >> 3, lx = lane & 7;
     const bool lane_in = ly >= 1 && lx >= 1;
@@ -420,52 +527,24 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
     const long long obs_stride = p.N * p.obs_elems;
     float *obs_t = p.obs + env * p.obs_elems;
 
+    WURM_TL_LAP(5);
     for (long long t0 = 0; t0 < p.T; t0 += 64) {
         const int nt = (int)min((long long)64, p.T - t0);
-        const long long my_t = t0 + lane;
-        long long my_a = lane < nt ? load_action(p.actions, p.act_dtype, my_t * p.N + env) : 0;
-        asm volatile("" : "+v"(my_a)); // retire the load here, not in front of the first readlane of the step loop
-        // Moves of step t0 + lane for each of the four orientations the snake may have by then, 16 bits each:
-        // next orientation << 4 | (code step & 63) << 6 | (sanitised action (single_snake.py:221-222) & 7) << 12, the
-        // step being -TAP[action] (:225-233); bits 0-3 are zero, so the low 6 bits of an entry are the shift that picks
-        // the NEXT step's entry.  The step loop reads both words with readlanes that do not depend on the state.
-        int my_mov01, my_mov23;
-        {
-            const auto entry = [](int a_out) {
-                const int ai = a_out & 3;
-                return ((ai ^ 2) << 4) | (((-tap_y(ai) * 8 - tap_x(ai)) & 63) << 6) | ((a_out & 7) << 12);
-            };
-            const bool in_range = my_a >= 0 && my_a < 4;
-            const int a_small = in_range ? (int)my_a : 7, a_mod = (int)(my_a % 4);
-            int me[4];
-#pragma unroll
-            for (int o = 0; o < 4; ++o)
-                me[o] = entry(o == a_small ? (o ^ 2) : a_mod);
-            my_mov01 = me[0] | (me[1] << 16);
-            my_mov23 = me[2] | (me[3] << 16);
-        }
-        const u64 my_call = p.call + 2ull * (u64)my_t; // step t uses call0 + 2t, its reset call0 + 2t + 1
+        int my_mov01, my_mov23, my_food; // my_food, RNG: the word the food cell is drawn with; INJ: the food code itself (-1: none)
         S9Reset my_reset;
-        int my_food; // RNG: the word the food cell is drawn with; INJ: the food code itself (-1: none)
-        if constexpr (INJ) {
-            // recorded outcomes of step t0 + lane, converted to cell codes 8 * row + column (reset_core's layout of inj[])
-            int sy = 4, sx = 4, d = 0, fc = -1, fe = -1;
-            if (lane < nt) {
-                const int *ir = p.inject_reset + (my_t * p.N + env) * 4;
-                sy = ir[0]; sx = ir[1]; d = ir[2]; fc = ir[3];
-                fe = p.inject_food[my_t * p.N + env];
-            }
-            asm volatile("" : "+v"(sy), "+v"(sx), "+v"(d), "+v"(fc), "+v"(fe)); // retire the loads before the step loop
-            d &= 3;
-            const int sc = sy * 8 + sx, dc = tap_y(d) * 8 + tap_x(d);
-            const int fcy = div_size(max(fc, 0), g.rcpS), fey = div_size(max(fe, 0), g.rcpS);
-            const int fcode = (fc >= 0 && fc < S * S) ? fcy * 8 + (fc - fcy * S) : -1;
-            my_reset.a = d | (fcode << 2);
-            my_reset.b = (sc + dc) | (sc << 7) | ((sc - dc) << 14);
-            my_food = (fe >= 0 && fe < S * S) ? fey * 8 + (fe - fey * S) : -1;
+        if constexpr (PAIR) {
+            const int *cb = pair_lds + (int)((t0 >> 6) & 1) * PAIR_CHUNK + lane;
+            my_mov01 = cb[0]; my_mov23 = cb[64]; my_reset.a = cb[128]; my_reset.b = cb[192]; my_food = cb[256];
+            // retire the reads here, not in front of the first readlane of the step loop
+            asm volatile("" : "+v"(my_mov01), "+v"(my_mov23), "+v"(my_reset.a), "+v"(my_reset.b), "+v"(my_food));
+            WURM_TL_LAP(1);
         } else {
-            my_reset = s9_reset_draw(p.seed, my_call + 1ull, env_id);
-            my_food = (int)rng_words(p.seed, my_call, env_id, RNG_FOOD, 0).w[0];
+            const S9Chunk ch = chunk_draw(t0, nt);
+            my_mov01 = ch.mov01; my_mov23 = ch.mov23; my_reset = ch.reset; my_food = ch.food;
+#ifdef WURM_TIMELINE
+            asm volatile("" : "+v"(my_mov01), "+v"(my_mov23), "+v"(my_reset.a), "+v"(my_reset.b), "+v"(my_food));
+#endif
+            WURM_TL_LAP(2);
         }
         // what lane j keeps of step t0 + j: its move entry, whether it ate, self collision | edge collision << 1
         int my_rec = 0, my_ate = 0, my_fl = 0;
@@ -604,15 +683,16 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
             for (int u = 0; u < U; ++u) step(j + u);
         }
         for (; j < nt; ++j) step(j);
-        if (lane < nt) {
-            const long long i = my_t * p.N + env;
-            store_action(p.actions, p.act_dtype, i, (long long)((my_rec << 17) >> 29));
-            p.reward[i] = my_ate ? 1.0f : 0.0f;
-            p.done[i] = (uint8_t)(my_fl != 0);
-            p.selfc[i] = (uint8_t)(my_fl & 1);
-            p.edgec[i] = (uint8_t)(my_fl >> 1);
+        WURM_TL_LAP(3);
+        if constexpr (PAIR) {
+            pair_lds[PAIR_REC + (int)((t0 >> 6) & 1) * 64 + lane] = ((my_rec >> 12) & 7) | (my_ate << 3) | (my_fl << 4);
+            pair_barrier(); // B(k+1)
+        } else {
+            flush(t0, nt, (my_rec << 17) >> 29, my_ate, my_fl);
         }
+        WURM_TL_LAP(4);
     }
+    if (OBSK == WURM_OBS_PARTIAL) WURM_TL_STORE(p.obs + env * p.obs_elems, lane);
     if (lane_in) { // the ring was empty and still is
         envp[my_cell] = lane == foodc ? 1.0f : 0.0f;
         envp[S * S + my_cell] = lane == c ? 1.0f : 0.0f;

@@ -20,6 +20,7 @@ enum Kind { K_STEP, K_RESET, K_OBSERVE, K_ROLLOUT, K_FUSED };
 //   rollout          | snake, S = 10 / 11, N >= lane_rollout_min_envs, lane_wide_eligible              | R_LANE_WIDE   lane_wide.hpp (default, one_channel, partial_2 / 3, positions, none)
 //   rollout          | snake, S == 9, both inject arrays, partial_n (n <= 3) or none                  | R_S9_INJ      rollout_s9_kernel<., true>
 //   rollout          | snake, S == 9, RNG mode, partial_n (n <= 3) or none                            | R_S9          rollout_s9_kernel
+//                    |   (both rows: N <= s9_pair_max_envs launches the kernel's pair form, two waves per env)
 //   rollout          | snake, S = 10 / 11, RNG mode, partial_n (n <= 3) or none                       | R_LEAN        rollout_lean_kernel
 //   rollout          | snake, S <= 11, RNG mode, partial_n (n <= 6) / none                            | R_GENERIC_PARTIAL / R_GENERIC_NONE (mode as template argument)
 //   rollout          | gridworld, RNG mode, N >= lane_rollout_min_envs, gridworld_lane_eligible        | R_GRIDWORLD_LANE gridworld_lane.hip (+ generic for the rest)
@@ -30,6 +31,8 @@ enum Route { R_GENERIC, R_GRID_STEP, R_LANE_STEP, R_GRID_ROLLOUT, R_LANE_ROLLOUT
 // (wurm_single_last_route: the route of the CALLING THREAD's last launch — a diagnostic the tests and bench.py name a launch by; no
 // state that a later call depends on.  Defined in single_snake.hip.)
 extern thread_local Route last_route;
+// (wurm_single_last_waves_per_env: 2 if that launch was rollout_s9_kernel's pair form, else 1)
+extern thread_local int last_waves_per_env;
 
 static const char *route_name(Route r)
 {
@@ -81,6 +84,7 @@ static hipError_t launch_one(Kind kind, const StepArgs &p, dim3 grid, dim3 block
     (void)hipGetLastError(); // drop any stale error left by earlier runtime calls of this thread
     const Route route = route_of(kind, SNAKE, CPL, p);
     last_route = route;
+    last_waves_per_env = 1;
     // (the one-env-per-wave code behind a grid / lane kernel, for the envs that one could not take: flagged_kernel, a wave per 64 envs)
     const unsigned wpb_f = block.x / 64u;
     const dim3 fgrid((unsigned)((p.N + 64ll * wpb_f - 1) / (64ll * wpb_f)));
@@ -128,15 +132,27 @@ static hipError_t launch_one(Kind kind, const StepArgs &p, dim3 grid, dim3 block
         }
         break;
     case R_S9_INJ:
-        if constexpr (SNAKE && CPL == 2) {
-            if (p.obs_mode == WURM_OBS_NONE) WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_NONE, true>), grid, block, lds, st, p);
-            else WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_PARTIAL, true>), grid, block, lds, st, p);
-        }
-        break;
     case R_S9:
         if constexpr (SNAKE && CPL == 2) {
-            if (p.obs_mode == WURM_OBS_NONE) WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_NONE>), grid, block, lds, st, p);
-            else WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_PARTIAL>), grid, block, lds, st, p);
+            const bool inj = route == R_S9_INJ, none = p.obs_mode == WURM_OBS_NONE;
+            if (p.N <= opt.s9_pair_max_envs) {
+                // the pair form: a workgroup of two waves per env, stepper and helper, and the helper's buffers behind
+                // the stepper's lds_per_wave bytes (single_kernels.hpp: 2 chunk buffers of 5 x 64 dwords, 2 record
+                // buffers of 64, the verdict)
+                const dim3 pgrid((unsigned)p.N), pblock(128);
+                const size_t plds = (size_t)p.lds_per_wave + (2 * 5 * 64 + 2 * 64 + 4) * sizeof(int);
+                last_waves_per_env = 2;
+                if (inj && none) WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_NONE, true, true>), pgrid, pblock, plds, st, p);
+                else if (inj) WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_PARTIAL, true, true>), pgrid, pblock, plds, st, p);
+                else if (none) WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_NONE, false, true>), pgrid, pblock, plds, st, p);
+                else WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_PARTIAL, false, true>), pgrid, pblock, plds, st, p);
+            } else if (inj) {
+                if (none) WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_NONE, true>), grid, block, lds, st, p);
+                else WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_PARTIAL, true>), grid, block, lds, st, p);
+            } else {
+                if (none) WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_NONE>), grid, block, lds, st, p);
+                else WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_PARTIAL>), grid, block, lds, st, p);
+            }
         }
         break;
     case R_LEAN:

@@ -241,6 +241,14 @@ __device__ __forceinline__ int tap_x(int i) { return i == 1 ? 1 : (i == 3 ? -1 :
 #ifdef WURM_TIMELINE
 #define WURM_TL_DECL unsigned long long tl_0 = 0, tl_1 = 0, tl_2 = 0, tl_3 = 0, tl_4 = 0, tl_5 = 0, tl_6 = 0, tl_7 = 0
 #define WURM_TL(k) tl_##k = __builtin_amdgcn_s_memtime()
+// rollouts (rollout_s9_kernel, tools/kernel_timeline.py --kernel s9): slot k is a TOTAL over the launch — the time since the
+// wave's previous lap (kept in slot 6) is added to it
+#define WURM_TL_LAP(k)                                                                                                   \
+    do {                                                                                                                 \
+        const unsigned long long tl_now = __builtin_amdgcn_s_memtime();                                                  \
+        tl_##k += tl_now - tl_6;                                                                                         \
+        tl_6 = tl_now;                                                                                                   \
+    } while (0)
 #define WURM_TL_STORE(ptr, lane)                                                                                         \
     do {                                                                                                                 \
         __builtin_amdgcn_s_waitcnt(0);                                                                                   \
@@ -285,6 +293,7 @@ __device__ __forceinline__ int tap_x(int i) { return i == 1 ? 1 : (i == 3 ? -1 :
 #else
 #define WURM_TL_DECL
 #define WURM_TL(k)
+#define WURM_TL_LAP(k)
 #define WURM_TL_STORE(ptr, lane)
 #define WURM_TLS(cx, k)
 #define WURM_TLS_INIT(cx)

@@ -9,8 +9,10 @@ One line per unit: kernels, identical code, identical descriptors, the demangled
 A kernel that only changed its NAME (it became the instantiation of a template, say) is compared with its successor when
 told so: --alias BASE_SYMBOL=HEAD_SYMBOL (mangled names; may be repeated) reads the base's assembly with the one name
 written as the other.
+Another flavour of the library (the Makefile's `timeline` and `probe` targets) is compared with --define NAME (may be
+repeated): both trees are compiled with -DNAME, and the header line says so.
 
-usage: tools/isa_identity.py BASE_REV [--jobs N] [--keep DIR [--reuse]] [--alias OLD=NEW] > profiles/rNN_isa_identity.txt    (exit status 1 on a difference)"""
+usage: tools/isa_identity.py BASE_REV [--jobs N] [--keep DIR [--reuse]] [--alias OLD=NEW] [--define NAME] > profiles/rNN_isa_identity.txt    (exit status 1 on a difference)"""
 import argparse
 import os
 import re
@@ -23,8 +25,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FLAGS = '-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wno-unused-function --cuda-device-only -S'.split()
 
 
-def compile_unit(tree, unit, out):
-    r = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', *FLAGS, unit + '.hip', '-o', out],
+def compile_unit(tree, unit, out, defines=()):
+    r = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', *FLAGS, *defines, unit + '.hip', '-o', out],
                        cwd=os.path.join(tree, 'wurm_amd', 'csrc'), capture_output=True, text=True)
     if r.returncode != 0:
         sys.exit(f'{tree}: {unit}.hip does not compile\n{r.stderr[-4000:]}')
@@ -67,7 +69,10 @@ def main():
     ap.add_argument('--reuse', action='store_true', help='compare the assembly files --keep already holds, compile nothing')
     ap.add_argument('--alias', action='append', default=[], metavar='OLD=NEW',
                     help='a symbol of the base that the working tree has under another (mangled) name')
+    ap.add_argument('--define', action='append', default=[], metavar='NAME',
+                    help='compile both trees with -DNAME (WURM_TIMELINE, WURM_GROUP_PROBE: the other flavours of the library)')
     a = ap.parse_args()
+    defines = ['-D' + d for d in a.define]
     alias = [tuple(x.split('=', 1)) for x in a.alias]
     work = a.keep or tempfile.mkdtemp(prefix='isa_identity_')
     base_tree = os.path.join(work, 'base_tree')
@@ -80,9 +85,9 @@ def main():
     jobs += [(ROOT, u, os.path.join(work, 'head', u + '.s')) for u in units(ROOT)]
     if not a.reuse:
         with ThreadPoolExecutor(a.jobs) as ex:
-            list(ex.map(lambda j: compile_unit(*j), jobs))
+            list(ex.map(lambda j: compile_unit(*j, defines), jobs))
     rev = subprocess.run(['git', '-C', ROOT, 'rev-parse', '--short', a.base], capture_output=True, text=True).stdout.strip()
-    print(f'# device assembly of the working tree against {rev}: hipcc --offload-arch=gfx950 {" ".join(FLAGS)}')
+    print(f'# device assembly of the working tree against {rev}: hipcc --offload-arch=gfx950 {" ".join(FLAGS + defines)}')
     for old, new in alias:
         print(f'# base symbol {old} is compared as {new}')
     print(f'# {"unit":18s} {"kernels":>8s} {"same code":>10s} {"same descr":>11s}  differing / added / removed symbols')

@@ -135,6 +135,19 @@ __device__ __forceinline__ void shape_constants(MultiArgs &p, bool layout, int s
     }
 }
 
+// The prologue of a kernel: its own copy of the argument block with what the instantiation fixes written into it.
+// INJ = false: the launch draws its random outcomes itself, the injected-outcome branches fold away; OBS >= 0: the
+// observation mode is a constant; KT / ST / NT, layout, snap_buffers: shape_constants.
+template <bool INJ, int OBS, int KT, int ST, int NT>
+__device__ __forceinline__ MultiArgs kernel_args(const MultiArgs &p_in, bool layout, int snap_buffers = -1)
+{
+    MultiArgs p = p_in;
+    if (!INJ) p.has_inj = p.has_rinj = 0;
+    if (OBS >= 0) p.obs_mode = OBS;
+    shape_constants<OBS, KT, ST, NT>(p, layout, snap_buffers);
+    return p;
+}
+
 // bit k of the lane's mask <=> cell lane + 64 k lies on the border ring (:183-186): a property of the grid, worked out once
 // per kernel (class_write paints the ring last, over whatever sits there)
 __device__ __forceinline__ u64 border_bits(const Ctx &cx)
@@ -189,6 +202,17 @@ __device__ __forceinline__ int BV(const Ctx &cx, int s, int c)
 // alone with its latency at 16 waves/CU: few large batches of loads, not many small ones).
 constexpr int LOAD_CHUNK = 16;
 
+// The per-snake slots of an env with nothing in it yet, by threads 0 .. K - 1: where a load starts, and all that is done for
+// an env that is about to be rebuilt — it is not read, the rest is multi_reset_grid(rebuild).  No sync: the caller's.
+__device__ __forceinline__ void clear_snake_slots(const Ctx &cx, int tid)
+{
+    if (tid < cx.K) {
+        cx.hcell[tid] = -1;
+        cx.lmax[tid] = 0;
+        cx.tclk[tid] = 0;
+    }
+}
+
 // plain (out if want_plain, wave-uniform; a reference, not a pointer: a conditional pointer to a local puts it in scratch):
 // the planes held nothing the LDS image cannot represent — food and head values 0 / 1,
 // at most one head per snake, body values integers in 0 .. 0x7fff — so lds_check sees all there is to check.
@@ -198,11 +222,7 @@ __device__ __forceinline__ u64 load_env(const Ctx &cx, const float *__restrict__
 {
     const int C = cx.C, lane = cx.lane, KC = cx.K * C;
     int odd = 0, nheads = 0;
-    if (lane < cx.K) {
-        cx.hcell[lane] = -1;
-        cx.lmax[lane] = 0;
-        cx.tclk[lane] = 0; // values are loaded as they are: ex = value
-    }
+    clear_snake_slots(cx, lane); // (clocks 0: values are loaded as they are, ex = value)
     for (int c = lane; c < C; c += 64) cx.hmap[c] = 0;
     wave_lds_sync();
     const float rcpC = 1.0f / (float)C;
@@ -263,6 +283,14 @@ __device__ __forceinline__ u64 load_env(const Ctx &cx, const float *__restrict__
     return load_env(cx, foodp, headp, bodyp, false, unused);
 }
 
+// A head cell that moved, in a sparse write-back: snake s's head plane has it at hc0 (-1: nowhere), it is at hc now.
+__device__ __forceinline__ void store_moved_head(float *__restrict__ headp, int C, int s, int hc0, int hc)
+{
+    float *hp = headp + (size_t)s * C;
+    if (hc0 >= 0) hp[hc0] = 0.0f;
+    if (hc >= 0) hp[hc] = 1.0f;
+}
+
 // LDS -> HBM: body cells flagged DIRTY, the two head cells that changed, food cells that changed.
 // t0_in_lmax: the clocks the snakes had when the env was loaded are in cx.lmax (a state that came from the mirror keeps
 // its clocks between calls); else they were 0 (load_env).
@@ -285,11 +313,7 @@ __device__ __forceinline__ void store_env(const Ctx &cx, float *__restrict__ foo
             }
         }
     }
-    if (!full && lane < cx.K && hc != hc0) {
-        float *hp = headp + (size_t)lane * C;
-        if (hc0 >= 0) hp[hc0] = 0.0f;
-        if (hc >= 0) hp[hc] = 1.0f;
-    }
+    if (!full && lane < cx.K && hc != hc0) store_moved_head(headp, C, lane, hc0, hc);
     for (int k = 0; k < cx.cpl; ++k) {
         int c = lane + 64 * k;
         if (c < C) {

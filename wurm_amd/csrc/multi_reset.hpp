@@ -152,6 +152,14 @@ __device__ __forceinline__ bool reroll_colour(const MultiArgs &p, long long agen
     return true;
 }
 
+// a re-rolled colour to HBM (load_colour reads it back)
+__device__ __forceinline__ void store_colour(const MultiArgs &p, long long agent, const Snake &sn)
+{
+    p.colours[agent * 3] = sn.col[0];
+    p.colours[agent * 3 + 1] = sn.col[1];
+    p.colours[agent * 3 + 2] = sn.col[2];
+}
+
 // The respawn search from the map of cell codes the step left (cell_codes + put_food: Snake::cmap_ok) — any state, any
 // size: a cell is occupied iff its code is neither 0 nor the ring's (what sits ON the ring never matters: a spawn cell is
 // at least 2 from the border, so its 3 x 3 neighbourhood stops at row / column 1).  Ten ballots give the occupancy of the

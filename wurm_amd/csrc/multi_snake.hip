@@ -21,6 +21,10 @@
 // The device functions are in headers by role, each in front of what calls it (no declaration ahead of a definition):
 // multi_device.hpp, multi_observe.hpp (the observation writers), multi_reset.hpp.  Here: the transition and the glue of a
 // step, every __global__ kernel, which kernel serves a call (multi_plan), its launch, and the extern "C" entry points.
+// Phases that several kernels run the same way are written once: kernel_args (a kernel's prologue), clear_snake_slots (an
+// env about to be rebuilt) and store_moved_head in multi_device.hpp, store_colour in multi_reset.hpp.
+// The entry, the action staging, the reset after a step and the exit of the two rollouts, the check mask behind obs_after
+// and the Snake initialisation of the reset kernels are still written per kernel: DESIGN.md section 4 says why.
 #include <cstdio>
 
 #include "multi_reset.hpp"
@@ -365,11 +369,7 @@ __device__ __forceinline__ void step_middle(const Ctx &cx, const MultiArgs &p, l
         if (rebuild) sn.done = false; // :798
         if (in) { sn.col[0] = in->col[0]; sn.col[1] = in->col[1]; sn.col[2] = in->col[2]; }
         else load_colour(p, agent, snake, sn);
-        if (snake && reroll_colour(p, agent, sn.done, env_id, p.pre_call, 0, sn)) {
-            p.colours[agent * 3] = sn.col[0];
-            p.colours[agent * 3 + 1] = sn.col[1];
-            p.colours[agent * 3 + 2] = sn.col[2];
-        }
+        if (snake && reroll_colour(p, agent, sn.done, env_id, p.pre_call, 0, sn)) store_colour(p, agent, sn);
         const bool respawn = p.cfg.respawn_any && ballot(snake && sn.done) != 0;
         if (rebuild || respawn) {
             bool orient_dirty = false;
@@ -448,10 +448,7 @@ __device__ __forceinline__ void workgroup_handoff()
 template <bool INJ = true, int OBS = -1, int KT = 0, int ST = 0, int NT = -1>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(KT > 0 ? 4 : 1))) void multi_step_kernel(MultiArgs p_in)
 {
-    MultiArgs p = p_in;
-    if (!INJ) p.has_inj = p.has_rinj = 0;
-    if (OBS >= 0) p.obs_mode = OBS;
-    shape_constants<OBS, KT, ST, NT>(p, true);
+    const MultiArgs p = kernel_args<INJ, OBS, KT, ST, NT>(p_in, true);
     const int wave = (int)(threadIdx.x >> 6), wpb = (int)(blockDim.x >> 6);
     const long long env0 = xcd_block(blockIdx.x, gridDim.x) * wpb, env = env0 + wave;
     const bool grouped = p.grp_emit != 0;
@@ -526,7 +523,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(KT > 0 ? 4 
         if (!from_mirror) fbits0 = load_env(cx, foodp, headp, bodyp, p.err != nullptr, plain);
     } else {
         fbits0 = 0;
-        if (snake) { cx.hcell[lane] = -1; cx.lmax[lane] = 0; cx.tclk[lane] = 0; } // the rest: multi_reset_grid(rebuild)
+        clear_snake_slots(cx, lane);
         wave_lds_sync();
     }
     t0 = snake ? cx.tclk[lane] : 0; // the clocks as loaded (0 unless the state came from the mirror)
@@ -612,11 +609,7 @@ __device__ __forceinline__ u64 wg_load_env(const Ctx &cx, const float *__restric
 {
     const int C = cx.C, KC = cx.K * C;
     int odd = 0, nheads = 0;
-    if (tid < cx.K) {
-        cx.hcell[tid] = -1;
-        cx.lmax[tid] = 0;
-        cx.tclk[tid] = 0;
-    }
+    clear_snake_slots(cx, tid);
     for (int c = tid; c < C; c += nth) cx.hmap[c] = 0;
     __syncthreads();
     const float rcpC = 1.0f / (float)C;
@@ -732,10 +725,7 @@ __device__ __forceinline__ void wg_observe_snap(const Ctx &cx, const MultiArgs &
 template <bool INJ = true, int OBS = -1, int KT = 0, int ST = 0>   // (INJ = false: as multi_rollout_kernel — the launch draws its own random outcomes)
 __global__ __launch_bounds__(256) void multi_step_wg_kernel(MultiArgs p_in)
 {
-    MultiArgs p = p_in;
-    if (!INJ) p.has_inj = p.has_rinj = 0;
-    if (OBS >= 0) p.obs_mode = OBS;
-    shape_constants<OBS, KT, ST, -1>(p, true);
+    const MultiArgs p = kernel_args<INJ, OBS, KT, ST, -1>(p_in, true);
     const int tid = (int)threadIdx.x, nth = (int)blockDim.x, wave = uniform(tid >> 6);
     const long long env = xcd_block(blockIdx.x, gridDim.x);
     if (env >= p.N) return; // the whole workgroup: the barriers below see every wave or none
@@ -759,7 +749,7 @@ __global__ __launch_bounds__(256) void multi_step_wg_kernel(MultiArgs p_in)
         if (!from_mirror) fbits0 = wg_load_env(cx, foodp, headp, bodyp, tid, nth, p.err != nullptr, plain);
     } else {
         fbits0 = 0;
-        if (tid < K) { cx.hcell[tid] = -1; cx.lmax[tid] = 0; cx.tclk[tid] = 0; }
+        clear_snake_slots(cx, tid);
     }
     __syncthreads();
     const int t0 = tid < K ? cx.tclk[tid] : 0;
@@ -794,11 +784,7 @@ __global__ __launch_bounds__(256) void multi_step_wg_kernel(MultiArgs p_in)
             __syncthreads();
         }
         wg_store_env(cx, foodp, headp, bodyp, fbits0, rebuild, tid, nth, from_mirror);
-        if (wave == 0 && !rebuild && lane < K && sn.hc != hc0) { // the head cells that moved
-            float *hp = headp + (size_t)lane * C;
-            if (hc0 >= 0) hp[hc0] = 0.0f;
-            if (sn.hc >= 0) hp[sn.hc] = 1.0f;
-        }
+        if (wave == 0 && !rebuild && lane < K && sn.hc != hc0) store_moved_head(headp, C, lane, hc0, sn.hc);
     }
     if (mirrored) {
         if (wave == 0 && rebase_clocks(cx) && lane == 0) cx.hmap[0] = 1; // (the head map is all-zero here: a flag for the others)
@@ -867,11 +853,7 @@ __global__ __launch_bounds__(256) void multi_reset_kernel(MultiArgs p)
     const bool want_obs = p.obs_mode != WURM_OBS_NONE;
 
     load_colour(p, agent, snake && (want_obs || p.cfg.colour_random), sn);
-    if (snake && reroll_colour(p, agent, sn.done, env_id, p.call, 0, sn)) {
-        p.colours[agent * 3] = sn.col[0];
-        p.colours[agent * 3 + 1] = sn.col[1];
-        p.colours[agent * 3 + 2] = sn.col[2];
-    }
+    if (snake && reroll_colour(p, agent, sn.done, env_id, p.call, 0, sn)) store_colour(p, agent, sn);
     if (!rebuild && !respawn && !want_obs) return;
 
     int hc0 = -1;
@@ -944,16 +926,12 @@ __global__ __launch_bounds__(256) void multi_reset_wg_kernel(MultiArgs p)
     sn.boosted = false;
     if (wave == 0) {
         load_colour(p, agent, snake && (want_obs || p.cfg.colour_random), sn);
-        if (snake && reroll_colour(p, agent, sn.done, env_id, p.call, 0, sn)) {
-            p.colours[agent * 3] = sn.col[0];
-            p.colours[agent * 3 + 1] = sn.col[1];
-            p.colours[agent * 3 + 2] = sn.col[2];
-        }
+        if (snake && reroll_colour(p, agent, sn.done, env_id, p.call, 0, sn)) store_colour(p, agent, sn);
     }
     if (!rebuild && !respawn && !want_obs) return;
     u64 fbits0 = 0;
     if (!rebuild) fbits0 = wg_load_env(cx, foodp, headp, bodyp, tid, nth);
-    else if (tid < K) { cx.hcell[tid] = -1; cx.lmax[tid] = 0; cx.tclk[tid] = 0; }
+    else clear_snake_slots(cx, tid);
     __syncthreads();
     int hc0 = -1;
     if (wave == 0) {
@@ -972,11 +950,7 @@ __global__ __launch_bounds__(256) void multi_reset_wg_kernel(MultiArgs p)
     __syncthreads();
     if (rebuild || respawn) {
         wg_store_env(cx, foodp, headp, bodyp, fbits0, rebuild, tid, nth);
-        if (snake && !rebuild && sn.hc != hc0) {
-            float *hp = headp + (size_t)lane * C;
-            if (hc0 >= 0) hp[hc0] = 0.0f;
-            if (sn.hc >= 0) hp[sn.hc] = 1.0f;
-        }
+        if (snake && !rebuild && sn.hc != hc0) store_moved_head(headp, C, lane, hc0, sn.hc);
     }
     if (want_obs) wg_observe_snap(cx, p, p.obs, env, tid, nth, wave);
 }
@@ -1014,10 +988,7 @@ __global__ __launch_bounds__(256) void multi_observe_wg_kernel(MultiArgs p)
 template <bool TWO, bool INJ, int OBS = -1, int KT = 0, int ST = 0, int NT = -1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void multi_rollout_kernel(MultiArgs p_in)
 {
-    MultiArgs p = p_in;
-    if (!INJ) p.has_inj = p.has_rinj = 0;
-    if (OBS >= 0) p.obs_mode = OBS;
-    shape_constants<OBS, KT, ST, NT>(p, !TWO && (OBS == WURM_OBS_PARTIAL || OBS == WURM_OBS_NONE), 0);
+    const MultiArgs p = kernel_args<INJ, OBS, KT, ST, NT>(p_in, !TWO && (OBS == WURM_OBS_PARTIAL || OBS == WURM_OBS_NONE), 0);
     const int wave = uniform((int)(threadIdx.x >> 6)), wpb = TWO ? 1 : (int)(blockDim.x >> 6);
     const long long env = xcd_block(blockIdx.x, gridDim.x) * wpb + (TWO ? 0 : wave);
     if (env >= p.N) return;
@@ -1120,11 +1091,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void m
         p.dones[agent] = (uint8_t)sn.done;
         p.orientations[agent] = sn.orient;
         if (p.boost_state) p.boost_state[agent] = (uint8_t)sn.boosted;
-        if (col_dirty) {
-            p.colours[agent * 3] = sn.col[0];
-            p.colours[agent * 3 + 1] = sn.col[1];
-            p.colours[agent * 3 + 2] = sn.col[2];
-        }
+        if (col_dirty) store_colour(p, agent, sn);
         cx.hcell[lane] = sn.hc;
     }
     wave_lds_sync();
@@ -1370,11 +1337,7 @@ __global__ __launch_bounds__(64 * (G / EPS + W)) __attribute__((amdgpu_waves_per
             p.dones[agent] = (uint8_t)sn.done;
             p.orientations[agent] = sn.orient;
             if (p.boost_state) p.boost_state[agent] = (uint8_t)sn.boosted;
-            if (col_dirty) {
-                p.colours[agent * 3] = sn.col[0];
-                p.colours[agent * 3 + 1] = sn.col[1];
-                p.colours[agent * 3 + 2] = sn.col[2];
-            }
+            if (col_dirty) store_colour(p, agent, sn);
             cx.hcell[lane] = sn.hc;
         }
         wave_lds_sync();

@@ -1,0 +1,68 @@
+"""Multi-agent A2C with a feed-forward policy per species, on this project's HIP paths end to end: the acting loop of the
+reference's experiments/multiagent.py:350-378 is `MultiSnake.act_window` (two launches per step: one `act` for every
+snake of every species, one `step` with the postponed reset), the learners are one `FusedA2CPopulation` with a member per
+species (three launches per window).
+
+    python examples/a2c_multi_species.py --num-envs 512 --n-agents 4 --n-species 2 --total-steps 200000
+    python examples/a2c_multi_species.py --num-envs 8 --n-agents 2 --n-species 2 --size 12 --total-steps 640   # tiny
+
+The policy has the four moves of `FeedforwardAgent`; the env runs with boost=False.
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from wurm_amd.agents import FeedforwardAgent  # noqa: E402
+from wurm_amd.envs import MultiSnake  # noqa: E402
+from wurm_amd.rl import FusedA2CPopulation  # noqa: E402
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--num-envs', type=int, default=512)
+    ap.add_argument('--n-agents', type=int, default=4)
+    ap.add_argument('--n-species', type=int, default=2)
+    ap.add_argument('--size', type=int, default=25)
+    ap.add_argument('--update-steps', type=int, default=20)
+    ap.add_argument('--total-steps', type=int, default=200000, help='env steps summed over the batch')
+    ap.add_argument('--lr', type=float, default=1e-3)
+    ap.add_argument('--gamma', type=float, default=0.99)
+    ap.add_argument('--entropy', type=float, default=0.01)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--device', default='cuda')
+    args = ap.parse_args(argv)
+    N, K, P, T = args.num_envs, args.n_agents, args.n_species, args.update_steps
+    if K % P:
+        raise SystemExit('--n-species must divide --n-agents: a FusedA2CPopulation member owns equally many envs')
+    E = 3 * 11 * 11
+    torch.manual_seed(args.seed)
+    env = MultiSnake(num_envs=N, num_snakes=K, size=args.size, observation_mode='partial_5', device=args.device,
+                     boost=False, food_mode='random_rate', respawn_mode='any', seed=args.seed)
+    agents = [FeedforwardAgent(num_actions=4, num_layers=2, hidden_units=64, num_inputs=E).to(env.device) for _ in range(P)]
+    learner = FusedA2CPopulation(agents, lr=args.lr, gamma=args.gamma, entropy_coef=args.entropy)
+    state = env.reset()
+    steps, window = 0, 0
+    while steps < args.total_steps:
+        out = env.act_window(learner.params, state, T)
+        x0 = torch.stack(list(state.values())).reshape(K * N, E)
+        res = learner.update(x0, out)
+        state = out['state']
+        steps += T * N
+        window += 1
+        if window % 10 == 1 or steps >= args.total_steps:
+            # per species, from the window tensors: a species owns the columns [s K/P N, (s + 1) K/P N)
+            reward = out['rewards'].view(T, P, -1).mean(dim=(0, 2)).tolist()
+            done = out['dones'].view(T, P, -1).float().mean(dim=(0, 2)).tolist()
+            vl, ent = res['value_loss'].tolist(), res['entropy'].tolist()
+            print(f'steps {steps:9d} | ' + ' | '.join(
+                f'species {s}: reward {reward[s]:+.4f} done {done[s]:.4f} value loss {vl[s]:.4f} entropy {ent[s]:.3f}'
+                for s in range(P)), flush=True)
+    return learner
+
+
+if __name__ == '__main__':
+    main()

@@ -583,6 +583,25 @@ int wurm_multi_check(const float *foods, const float *heads, const float *bodies
 int wurm_multi_colours(int16_t *colours, int64_t num_envs, int num_snakes, int fixed, uint64_t seed, uint64_t call,
                        int64_t env_offset, void *stream);
 
+/* The acting half of the multi-agent loop (experiments/multiagent.py:354-364) for every snake and every species in ONE
+ * launch: per (snake k, env i) row  probs, value = model_s(obs[k][i]);  action = Categorical(probs).sample()  with the
+ * 2 x 64 feed-forward actor-critic of species s = k * num_species / num_snakes (integer division, multiagent.py:356).
+ * Kernel: wurm_amd/csrc/multi_act.hpp.  The arithmetic is wurm_single_policy_rollout's, bit for bit.
+ *   params  (num_species, P) fp32, row s as pack_policy_params, P = 64 E + 64 + 4096 + 64 + 256 + 4 + 64 + 1
+ *   obs     (num_snakes, num_envs, E) fp32, contiguous: MultiSnake's 'partial_n' observations, agent-major as `step`
+ *           lays them out;  E = num_inputs = 3 (2n+1)^2, n <= 6
+ *   actions (num_snakes, num_envs) int64, written: 0..3 — the agent-major block wurm_multi_step reads
+ *   probs   (num_snakes, num_envs, 4) fp32, written, nullable;  values (num_snakes, num_envs) fp32, written, nullable
+ *   The uniform of row (k, i) is u01 of word 0 of Philox(seed; env = (env_offset + i) * num_snakes + k, call, purpose 8):
+ *   `call` is a POLICY call counter the caller keeps beside the env's own; this entry point consumes none of the latter.
+ * Refused before any HIP call: negative sizes, num_species < 1 or > num_snakes (so num_snakes = 0 is refused), and — with
+ * num_envs > 0 — null params, obs or actions (WURM_ERR_INVALID_ARG); a num_inputs that is not 3 (2n+1)^2 with n <= 6
+ * (WURM_ERR_UNSUPPORTED).  num_envs = 0 is a successful no-op without a launch.  Otherwise exactly one launch on
+ * `stream`, whatever the sizes; no atomics. */
+int wurm_multi_act(const float *params, const float *obs, int64_t *actions, float *probs, float *values,
+                   int64_t num_envs, int num_snakes, int num_species, int num_inputs, uint64_t seed, uint64_t call,
+                   int64_t env_offset, void *stream);
+
 /* wurm.utils.determine_orientations (wurm/utils.py:36-65) over a (n,3,S,S) batch; out (n) int64. */
 int wurm_orientations(const float *envs, int64_t *out, int64_t n, int size, void *stream);
 

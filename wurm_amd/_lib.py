@@ -36,6 +36,7 @@ SYMBOLS = [
     'wurm_a2c_ff_pop_apply', 'wurm_a2c_ff_pop_update', 'wurm_a2c_ff_pop_update_gae', 'wurm_a2c_ff_pop_exploit',
     'wurm_rollout_stats_workspace_bytes', 'wurm_rollout_stats',
     'wurm_single_rollout_frames', 'wurm_grid_rollout_frames',
+    'wurm_multi_act',
 ]
 
 

@@ -261,6 +261,9 @@ class MultiSnake(object):
             self.observation_size = 2 * int(observation_mode.split('_')[1]) + 1
         self.seed = _draw_seed() if seed is None else int(seed)
         self.env_offset = int(env_offset)
+        # the POLICY call counter: one per `act`, beside the env's own RNG counter (`_fs.call`), which `act` leaves alone.  A
+        # plain attribute: a copy / pickle carries it as it carries `_copy_call`.
+        self.policy_calls = 0
 
         if render_args is None:
             self.render_args = {'num_rows': 1, 'num_cols': 1, 'size': 256}
@@ -845,6 +848,37 @@ class MultiSnake(object):
         return {'observations': obs, 'rewards': out_f[:, 0], 'food': food, 'size': size,
                 'dones': out_b[:, 0], 'boost': out_b[:, 1], 'snake_collision': out_b[:, 2],
                 'edge_collision': out_b[:, 3], 'all_done': all_done}
+
+    # ------------------------------------------------------------------ acting (extension; wurm_amd/envs/_multi_act.py)
+
+    def act(self, params: torch.Tensor, observations, num_species: int = None) -> dict:
+        """`probs, value = models[species](obs); action = Categorical(probs).sample()` of every agent
+        (experiments/multiagent.py:354-364) in one launch: snake k acts with row k * num_species // num_snakes of `params`.
+
+        params: (num_species, num_params) fp32 on the env's device, rows in `pack_policy_params` order — or (num_params,)
+            for a single species; `FusedA2CPopulation.params` / `FusedA2CLearner.params` as they are.
+        observations: what `step` / `reset` returned (a dict agent_i -> (N, 3, w, w); used in place when its tensors are
+            consecutive views of one buffer, as theirs are), or a (K, N, 3, w, w) / (K, N, E) tensor.
+        num_species: default `params.shape[0]` (1 for 1-D params).
+        Returns {'actions': dict agent_i -> (N,) int64, ready for `step`; 'actions_t' (K, N), 'probs' (K, N, 4), 'values'
+        (K, N): the tensors the kernel wrote, of which the dict's values are views}.
+        Only 'partial_n' with n <= 6 and dtype=torch.float are served (NotImplementedError otherwise).  The draws are keyed by
+        `policy_calls`, which grows by one; the env's own counter, its state and a postponed reset are left alone."""
+        from wurm_amd.envs import _multi_act
+        return _multi_act.act(self, params, observations, num_species)
+
+    def act_window(self, params: torch.Tensor, state, num_steps: int, num_species: int = None) -> dict:
+        """`num_steps` iterations of the reference's acting loop (experiments/multiagent.py:354-378)
+            a = act(params, state); obs, r, d, info = step(a['actions']); reset(d['__all__'], return_observations=False);
+            state = obs
+        (the next policy input is the observation `step` returned, before the reset) — two launches per step.  Returns
+        tensors with columns k * N + i: `observations` (T, K N, E), `actions` (as sampled), `probs` (T, K N, 4), `values`,
+        `rewards`, `dones` (T, K N), `all_done` (T, N), and `state`, the last observations.  With one species per equal
+        block of snakes this is what `FusedA2CPopulation.update(state0.reshape(K N, E), out)` takes, one member per
+        species.  `actions`, `probs` and `values` are allocated once and written in place by `act`; what `step` returns
+        lives in its output slab and is gathered once behind the loop."""
+        from wurm_amd.envs import _multi_act
+        return _multi_act.act_window(self, params, state, num_steps, num_species)
 
     # ------------------------------------------------------------------ invariants
 

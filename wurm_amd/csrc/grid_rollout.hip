@@ -36,11 +36,7 @@ namespace {
 constexpr int NO_CELL_G = 1 << 20;
 constexpr int EX_RING = 0xffff;      // border ring and the padding behind the last cell
 constexpr int EX_FOOD = 0xfffe;
-#ifdef GRID_W32
-typedef int cell_t;
-#else
 typedef unsigned short cell_t;
-#endif
 constexpr int EX_MAX_BODY = 0x7000;  // a longer snake (impossible on a 64 x 64 grid) goes to the generic kernel
 constexpr int EX_REBASE = 0xc000;    // re-base the clocks once G passes this (a 64-step chunk adds at most 4 * 64)
 
@@ -48,10 +44,6 @@ typedef unsigned short ushort4v __attribute__((ext_vector_type(4)));
 typedef int int4v __attribute__((ext_vector_type(4)));
 
 struct Grid;
-#ifdef GRID_W32
-__device__ __forceinline__ int4v read4(const cell_t *ex, int c0) { return *(const int4v *)(ex + c0); }
-__device__ __forceinline__ void write4(cell_t *ex, int c0, const int4v &e) { *(int4v *)(ex + c0) = e; }
-#else
 __device__ __forceinline__ int4v read4(const cell_t *ex, int c0)
 {
     const ushort4v v = *(const ushort4v *)(ex + c0);
@@ -63,7 +55,6 @@ __device__ __forceinline__ void write4(cell_t *ex, int c0, const int4v &e)
     const ushort4v e16 = {(cell_t)e.x, (cell_t)e.y, (cell_t)e.z, (cell_t)e.w};
     *(ushort4v *)(ex + c0) = e16;
 }
-#endif
 typedef float float4v __attribute__((ext_vector_type(4)));
 
 struct Grid {
@@ -79,6 +70,9 @@ __device__ __forceinline__ bool ring_cell(const Grid &g, int c)
     const int y = div_size(c, g.rcpS), x = c - y * g.S;
     return y == 0 || x == 0 || y == g.S - 1 || x == g.S - 1;
 }
+
+// i-th row of a walk that starts at row g.rot and wraps: the order an observation is written in (WURM_GRID_ROTATE, make_grid)
+__device__ __forceinline__ int grid_rotated_row(const Grid &g, int i) { return i + g.rot < g.iters ? i + g.rot : i + g.rot - g.iters; }
 
 // K-th cell (row-major) with ex <= T — a free interior cell: markers and live clocks are > T — with K = mulhi(word,
 // number of such cells): the choice add_food / fast_food_cell make (single_snake.py:306-320).  -1 if none is free.
@@ -175,8 +169,7 @@ __device__ __forceinline__ void grid_observe(const Grid &g, const StepView &s, f
             return;
         }
         for (int i = 0; i < g.iters; ++i) {
-            const int it = i + g.rot < g.iters ? i + g.rot : i + g.rot - g.iters;
-            const int c0 = it * 256 + 4 * lane;
+            const int c0 = grid_rotated_row(g, i) * 256 + 4 * lane;
             const int4v e = read4(g.ex, c0);
             float4v r, gr, b;
 #pragma unroll
@@ -191,8 +184,7 @@ __device__ __forceinline__ void grid_observe(const Grid &g, const StepView &s, f
         }
     } else if (mode == WURM_OBS_RAW) { // clone of the state: food, head, body
         for (int i = 0; i < g.iters; ++i) {
-            const int it = i + g.rot < g.iters ? i + g.rot : i + g.rot - g.iters;
-            const int c0 = it * 256 + 4 * lane;
+            const int c0 = grid_rotated_row(g, i) * 256 + 4 * lane;
             const int4v e = read4(g.ex, c0);
             float4v f, h, b;
 #pragma unroll
@@ -207,8 +199,7 @@ __device__ __forceinline__ void grid_observe(const Grid &g, const StepView &s, f
         }
     } else if (mode == WURM_OBS_ONE_CHANNEL) { // :142-151: 0.5 body + 0.5 head + 1.5 food, ring -1
         for (int i = 0; i < g.iters; ++i) {
-            const int it = i + g.rot < g.iters ? i + g.rot : i + g.rot - g.iters;
-            const int c0 = it * 256 + 4 * lane;
+            const int c0 = grid_rotated_row(g, i) * 256 + 4 * lane;
             const int4v e = read4(g.ex, c0);
             float4v v;
 #pragma unroll
@@ -533,6 +524,16 @@ __device__ __forceinline__ void mirror_grid_commit(const Grid &g, const cell_t *
     wave_lds_sync();
 }
 
+// this env leaves the domain: the generic kernel takes it on the planes (second launch, only_flagged), and its record in the
+// mirror, if there is one, no longer describes it
+__device__ __forceinline__ void grid_leave_domain(const StepArgs &p, bool mirrored, int *mrec, long long env, int lane)
+{
+    if (lane == 0) {
+        if (mirrored) mrec[9] = 0;
+        p.done[env] = GRID_SKIPPED;
+    }
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(256) void grid_rollout_kernel(StepArgs p)
 {
@@ -564,15 +565,12 @@ __global__ __launch_bounds__(256) void grid_rollout_kernel(StepArgs p)
                 mirror_load_grid(g, mgrid);
                 grid_observe<VEC>(g, view_of(s, hb), envp, WURM_OBS_RAW, 0);
             }
-            if (lane == 0) { mrec[9] = 0; p.done[env] = GRID_SKIPPED; }
+            grid_leave_domain(p, true, mrec, env, lane);
             return;
         }
     }
     if (!from_rec && !grid_load<VEC>(g, envp, s)) { // outside the domain: rollout_kernel takes this env (second launch, only_flagged)
-        if (lane == 0) {
-            if (mirrored) mrec[9] = 0;
-            p.done[env] = GRID_SKIPPED;
-        }
+        grid_leave_domain(p, mirrored, mrec, env, lane);
         return;
     }
 
@@ -716,13 +714,10 @@ __global__ __launch_bounds__(256) void grid_step_kernel(StepArgs p)
                 mirror_grid_commit(g, mgrid, gv);
                 grid_observe<VEC>(g, view_of(s, hb), envp, WURM_OBS_RAW, 0);
             }
-            if (lane == 0) { mrec[9] = 0; p.done[env] = GRID_SKIPPED; }
+            grid_leave_domain(p, true, mrec, env, lane);
             return;
         } else if (!grid_load<VEC>(g, envp, s)) {
-            if (lane == 0) {
-                if (mirrored) mrec[9] = 0;
-                p.done[env] = GRID_SKIPPED;
-            }
+            grid_leave_domain(p, mirrored, mrec, env, lane);
             return;
         }
     }
@@ -860,52 +855,54 @@ static bool grid_aligned(const StepArgs &p)
            ((uintptr_t)p.obs_after % 16 == 0) && (p.obs_elems % 4 == 0 || plain);
 }
 
+// The launch shape of the three kernels: one wave per env, one wave per workgroup up to 4096 envs and four above; lds: the
+// clock grids of a workgroup's waves
+struct GridGeometry {
+    int wpb; // waves per workgroup
+    dim3 block, grid;
+    size_t lds;
+};
+static GridGeometry grid_geometry(const StepArgs &p)
+{
+    const int C = p.S * p.S, iters = (C + 255) >> 8;
+    const int wpb = p.N <= 4096 ? 1 : 4;
+    return {wpb, dim3(64 * wpb), dim3((unsigned)((p.N + wpb - 1) / wpb)), (size_t)iters * 256 * sizeof(cell_t) * wpb};
+}
+
+static hipError_t grid_launch(void (*kernel)(StepArgs), const GridGeometry &q, hipStream_t stream, const StepArgs &p)
+{
+    (void)hipGetLastError();
+    WURM_LAUNCH(kernel, q.grid, q.block, q.lds, stream, p);
+    return hipGetLastError();
+}
+
 hipError_t launch_grid_rollout(const StepArgs &p_in, hipStream_t stream)
 {
     StepArgs p = p_in;
     p.grid_rotate = (int)opt.grid_rotate;
-    const int C = p.S * p.S, iters = (C + 255) >> 8;
-    const int wpb = p.N <= 4096 ? 1 : 4;
-    dim3 block(64 * wpb), grid((unsigned)((p.N + wpb - 1) / wpb));
-    size_t lds = (size_t)iters * 256 * sizeof(cell_t) * wpb;
+    GridGeometry q = grid_geometry(p);
     // Residency.  Dynamic LDS is the only per-launch handle on how many waves share a CU.  Measured on MI355X (BASELINE
     // configs[4], 16-step launches, median of 5 x 20 launches): 0.38-0.39 ms at 8-12 waves per CU, 0.39-0.46 ms with all
     // 32 resident — with every wave resident the launch runs in lockstep (all probing, then all storing) more often.
     // The effect is at the edge of the run-to-run noise; 12 is kept, WURM_GRID_WAVES_PER_CU overrides it.
     const int waves_per_cu = (int)std::max(1ll, opt.grid_waves_per_cu); // tuning knob
     const size_t per_wave_target = (160u * 1024u / (unsigned)waves_per_cu) & ~255u;
-    lds = std::min<size_t>(std::max(lds, per_wave_target * wpb), 64u * 1024u);
-    (void)hipGetLastError();
-    if (grid_aligned(p)) WURM_LAUNCH(grid_rollout_kernel<true>, grid, block, lds, stream, p);
-    else WURM_LAUNCH(grid_rollout_kernel<false>, grid, block, lds, stream, p);
-    return hipGetLastError();
+    q.lds = std::min<size_t>(std::max(q.lds, per_wave_target * q.wpb), 64u * 1024u);
+    return grid_launch(grid_aligned(p) ? grid_rollout_kernel<true> : grid_rollout_kernel<false>, q, stream, p);
 }
 
 hipError_t launch_grid_step(const StepArgs &p_in, hipStream_t stream)
 {
     StepArgs p = p_in;
     p.grid_rotate = (int)opt.grid_rotate;
-    const int C = p.S * p.S, iters = (C + 255) >> 8;
-    const int wpb = p.N <= 4096 ? 1 : 4;
-    dim3 block(64 * wpb), grid((unsigned)((p.N + wpb - 1) / wpb));
-    const size_t lds = (size_t)iters * 256 * sizeof(cell_t) * wpb; // one step per launch: as many waves per CU as fit
-    (void)hipGetLastError();
-    if (grid_aligned(p)) WURM_LAUNCH(grid_step_kernel<true>, grid, block, lds, stream, p);
-    else WURM_LAUNCH(grid_step_kernel<false>, grid, block, lds, stream, p);
-    return hipGetLastError();
+    // one step per launch: as many waves per CU as fit
+    return grid_launch(grid_aligned(p) ? grid_step_kernel<true> : grid_step_kernel<false>, grid_geometry(p), stream, p);
 }
 
-hipError_t launch_grid_resident_flush(const StepArgs &p_in, hipStream_t stream)
+hipError_t launch_grid_resident_flush(const StepArgs &p, hipStream_t stream)
 {
-    StepArgs p = p_in;
-    const int C = p.S * p.S, iters = (C + 255) >> 8;
-    const int wpb = p.N <= 4096 ? 1 : 4;
-    dim3 block(64 * wpb), grid((unsigned)((p.N + wpb - 1) / wpb));
-    const size_t lds = (size_t)iters * 256 * sizeof(cell_t) * wpb;
-    (void)hipGetLastError();
-    if (C % 4 == 0 && (uintptr_t)p.envs % 16 == 0) WURM_LAUNCH(grid_flush_kernel<true>, grid, block, lds, stream, p);
-    else WURM_LAUNCH(grid_flush_kernel<false>, grid, block, lds, stream, p);
-    return hipGetLastError();
+    const bool aligned = (p.S * p.S) % 4 == 0 && (uintptr_t)p.envs % 16 == 0;
+    return grid_launch(aligned ? grid_flush_kernel<true> : grid_flush_kernel<false>, grid_geometry(p), stream, p);
 }
 
 } // namespace wurm

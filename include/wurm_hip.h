@@ -85,6 +85,11 @@ const char *wurm_single_last_route(void);
  * Results do not depend on the form.  Diagnostic only (tests/test_s9_pair_rollout.py tells the two forms apart by it). */
 int wurm_single_last_waves_per_env(void);
 
+/* Which wave of that launch rendered the partial_n crops: 1 if it was the pair form whose helper wave renders them (the pair
+ * form above, partial_n, at least WURM_S9_CROP_HELPER_MIN_STEPS steps, default 256; -1 = never), else 0: the stepping wave,
+ * or a kernel without that split.  Results do not depend on it.  Diagnostic only (tests/test_s9_crop_helper.py). */
+int wurm_single_last_crop_wave(void);
+
 /* The same for MultiSnake: the kernel instantiation that served the calling thread's last wurm_multi_* launch, by its row in
  * the list in wurm_amd/csrc/multi_snake.hip ("step_rng_full_k4_s25", "rollout_two_rng", "rollout_group_8215_rng", "reset_wg",
  * ...; "none" before the first), followed by how it was driven where one kernel is driven in several ways: "+emit_wave" /

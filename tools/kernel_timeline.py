@@ -5,14 +5,18 @@ Needs the instrumented build of the library (s_memtime stamps, wurm_amd/csrc/wur
     make -C wurm_amd/csrc timeline          # -> wurm_amd/libwurm_hip_timeline.so (cross-compiles without a GPU)
     WURM_HIP_LIBRARY=$PWD/wurm_amd/libwurm_hip_timeline.so python tools/kernel_timeline.py [--kernel resident|lane_step]
                                                             [--envs 65536] [--epw 32] [--form ref|noobs]
-    ... python tools/kernel_timeline.py --kernel s9 [--envs 512] [--steps 1024] [--pair 0|1]
+    ... python tools/kernel_timeline.py --kernel s9 [--envs 512] [--steps 1024] [--pair 0|1] [--crop-helper 0|1]
 Every wave overwrites the first 64 bytes of its own observation block with eight stamps once its stores have drained; this
 script reads them back from the observation `step` returned and prints, per segment between two stamps, the distribution
 over the waves in s_memtime ticks — counters of different XCDs are not synchronised, so only differences within one wave
 are used.  The observations of a timeline run are garbage by construction.
 
 --kernel s9: the stepping wave of rollout_s9_kernel (the headline rollout, --envs x 9 x 9 'partial_2', --steps batch-steps per
-launch), one wave form (--pair 0) or pair form (--pair 1).  Its stamps are TOTALS over the launch's 64-step chunks."""
+launch), one wave form (--pair 0) or pair form (--pair 1).  Its stamps are TOTALS over the launch's 64-step chunks.
+--crop-helper 1 (with --pair 1, --steps above 64): the pair form whose helper wave renders the crops; the helper's own laps,
+which it leaves over the crop of step 1, are printed too: its rendering time per chunk against the stepper's stepping time
+per chunk, and what each wave waits at the chunk barrier.  (A library built with -DWURM_S9_CROP_SPP1 as well renders one
+step per pass whatever the window: the measurement the two-steps-per-pass renderer rests on.)"""
 import argparse
 import os
 import sys
@@ -27,6 +31,7 @@ ap.add_argument('--form', default='ref', choices=['ref', 'noobs'])
 ap.add_argument('--iters', type=int, default=12)
 ap.add_argument('--steps', type=int, default=1024, help='--kernel s9: batch-steps per launch')
 ap.add_argument('--pair', type=int, default=0, choices=[0, 1], help='--kernel s9: the pair form (two waves per env)')
+ap.add_argument('--crop-helper', type=int, default=0, choices=[0, 1], help='--kernel s9 --pair 1: the helper wave renders the crops')
 args = ap.parse_args()
 if 'timeline' not in os.environ.get('WURM_HIP_LIBRARY', ''):
     sys.exit('set WURM_HIP_LIBRARY to the instrumented library (see the docstring)')
@@ -37,7 +42,9 @@ def s9_timeline():
     """slots of rollout_s9_kernel's stepper (single_kernels.hpp): 0 entry, 7 end (stores drained); totals over the chunks:
     5 state load + setup, 1 wait for the chunk's inputs (one wave: the tape load, which also drains the previous chunk's
     observation stores; pair: the barrier and the LDS reads), 2 prologue arithmetic (one wave only), 3 step loop, 4 flush
-    (one wave: the record stores issued; pair: the record's LDS write and the barrier)"""
+    (one wave: the record stores issued; pair: the record's LDS write and the barrier, that is the stepper's wait for the helper).
+    Slots of the helper with --crop-helper 1: 1 tape load, draw and record stores (and, first, B0), 2 rendering of the chunk
+    before, 3 wait at the chunk barrier, 4 rendering of the last chunk, after the stepper has finished"""
     import numpy as np
     import torch
     from wurm_amd import _lib
@@ -46,19 +53,26 @@ def s9_timeline():
     T = args.steps
     env = SingleSnake(num_envs=N_, size=9, observation_mode='partial_2', device='cuda', seed=0)
     _lib.set_option('WURM_S9_PAIR_MAX_ENVS', (1 << 40) if args.pair else 0)
+    _lib.set_option('WURM_S9_CROP_HELPER_MIN_STEPS', 1 if args.crop_helper else -1)
+    assert not args.crop_helper or (args.pair and T > 64), '--crop-helper 1 needs --pair 1 and more than one chunk'
+    helper_rows = []
     g = torch.Generator(device='cuda').manual_seed(1)
     rows = []
     for it in range(args.iters):
         out = env.rollout(torch.randint(0, 4, (T, N_), device='cuda', generator=g))
         torch.cuda.synchronize()
         assert _lib.lib().wurm_single_last_waves_per_env() == 1 + args.pair
+        assert _lib.lib().wurm_single_last_crop_wave() == args.crop_helper
         obs = out['observations']
         if it >= 4:
             rows.append(obs[0].reshape(N_, -1)[:, :16].contiguous().view(torch.int64).cpu().numpy().astype(np.int64))
+            if args.crop_helper:
+                helper_rows.append(obs[1].reshape(N_, -1)[:, :16].contiguous().view(torch.int64).cpu().numpy().astype(np.int64))
     st = np.concatenate(rows)
     life = st[:, 7] - st[:, 0]
     st, life = st[(life > 0) & (life < 10 ** 9)], life[(life > 0) & (life < 10 ** 9)]
-    print(f'rollout_s9_kernel, {N_} envs x {T} steps, {"pair" if args.pair else "one-wave"} form: {len(life)} stepper samples; '
+    form = 'pair form, crops by the helper' if args.crop_helper else 'pair form' if args.pair else 'one-wave form'
+    print(f'rollout_s9_kernel, {N_} envs x {T} steps, {form}: {len(life)} stepper samples; '
           f's_memtime ticks, totals over {(T + 63) // 64} chunks')
     named = [(5, 'state load + setup'), (1, 'wait for the chunk inputs'), (2, 'prologue arithmetic'), (3, 'step loop'),
              (4, 'flush / hand-over')]
@@ -72,6 +86,23 @@ def s9_timeline():
     print(f'  wave lifetime: p10 {int(np.percentile(life, 10))}  p50 {int(np.median(life))}  p90 {int(np.percentile(life, 90))}  max {int(life.max())}')
     per_chunk = 100.0 * np.median(st[:, 1] + st[:, 2] + st[:, 4]) / np.median(life)
     print(f'  per-chunk work around the step loop (wait + prologue + flush): {per_chunk:.1f} % of p50 life')
+    if not args.crop_helper:
+        return
+    C = (T + 63) // 64
+    hs = np.concatenate(helper_rows)
+    hl = hs[:, 7] - hs[:, 0]
+    hs, hl = hs[(hl > 0) & (hl < 10 ** 9)], hl[(hl > 0) & (hl < 10 ** 9)]
+    print(f'helper wave: {len(hl)} samples')
+    for k, name in [(1, 'tape, draw, records (+ B0)'), (2, 'rendering, chunks 0 .. C-2'), (3, 'wait at the chunk barrier'),
+                    (4, 'rendering, last chunk')]:
+        c = hs[:, k]
+        print(f'  {name:>26s} p10 {int(np.percentile(c, 10)):7d}  p50 {int(np.median(c)):7d}  p90 {int(np.percentile(c, 90)):7d}  '
+              f'max {int(c.max()):7d}   {100.0 * np.median(c) / np.median(hl):5.1f} % of p50 life')
+    print(f'  wave lifetime: p10 {int(np.percentile(hl, 10))}  p50 {int(np.median(hl))}  p90 {int(np.percentile(hl, 90))}  max {int(hl.max())}')
+    print(f'per chunk, p50: the stepper steps {int(np.median(st[:, 3])) // C} ticks, the helper renders '
+          f'{int(np.median(hs[:, 2])) // max(C - 1, 1)} and does its other work in {int(np.median(hs[:, 1])) // C}; '
+          f'the stepper\'s hand-over and barrier wait is {100.0 * np.median(st[:, 4]) / np.median(life):.1f} % of its life, '
+          f'the helper\'s barrier wait {100.0 * np.median(hs[:, 3]) / np.median(hl):.1f} % of its own')
 
 
 if args.kernel == 's9':

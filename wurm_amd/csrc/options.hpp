@@ -25,6 +25,7 @@ struct Options {
     long long grid_rollout_min_size; // WURM_GRID_ROLLOUT_MIN_SIZE SingleSnake rollouts on LDS clock grids from this grid size on (-1 = by observation mode: 14 / 18 / 26; 12 = every size they serve)
     long long policy_wide;           // WURM_POLICY_WIDE           1 = fused actor on policy_wide_kernel even where policy_rollout.hpp's kernels serve (S <= 11, n <= 3)
     long long s9_pair_max_envs;      // WURM_S9_PAIR_MAX_ENVS      9 x 9 rollouts of small batches (rollout_s9_kernel): two waves per env, stepper and helper, up to this many envs (1024; 0 = always one wave per env)
+    long long s9_crop_helper_min_steps; // WURM_S9_CROP_HELPER_MIN_STEPS that pair form, partial_n: the helper wave renders the crops in launches of at least this many steps (256; -1 = never)
 };
 
 extern Options opt;

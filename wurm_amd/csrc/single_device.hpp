@@ -1138,6 +1138,57 @@ __device__ __forceinline__ int set_lane(int v, int value, int dst)
     return v;
 }
 
+// What the helper wave needs of step t0 + j to render its crop (rollout_s9_kernel, CROPH), each in lane j of its register: the
+// move entry, the head code, the food code the crop shows and the body mask without the head.  set_lane five times over
+// with ONE lane select in m0.
+struct S9CropRec {
+    int ent, c, food, body_lo, body_hi;
+};
+__device__ __forceinline__ void set_lane(S9CropRec &r, int ent, int c, int food, u64 body, int dst)
+{
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm" // (m0: as above)
+    asm("s_mov_b32 m0, %10\n\t"
+        "v_writelane_b32 %0, %5, m0\n\t"
+        "v_writelane_b32 %1, %6, m0\n\t"
+        "v_writelane_b32 %2, %7, m0\n\t"
+        "v_writelane_b32 %3, %8, m0\n\t"
+        "v_writelane_b32 %4, %9, m0"
+        : "+v"(r.ent), "+v"(r.c), "+v"(r.food), "+v"(r.body_lo), "+v"(r.body_hi)
+        : "s"(ent), "s"(c), "s"(food), "s"((int)(u32)body), "s"((int)(u32)(body >> 32)), "s"(dst)
+        : "m0");
+#pragma clang diagnostic pop
+}
+
+// The partial_n window cell a lane of the 9 x 9 rollout renders, for window-cell index wl (lanes past the window repeat
+// its last cell: same address, same value): its offset from the head in rows, columns and codes, what an occupied cell
+// shows in channel 1 there, and which head codes put it inside the ring.
+struct S9Window {
+    int w, dy0, dx0, code_d;
+    float green;
+    u64 live_tab; // bit (8 * row + column): with the head there, this window cell is inside the ring
+};
+__device__ __forceinline__ S9Window s9_window(int wl, int n)
+{
+    S9Window r;
+    const int W = 2 * n + 1, W2 = W * W;
+    r.w = min(wl, W2 - 1);
+    const int wy = div_size(r.w, 1.0f / (float)W), wx = r.w - wy * W;
+    r.dy0 = wy - n; r.dx0 = wx - n;            // window row / column offset from the head
+    r.code_d = r.dy0 * 8 + r.dx0;              // code of the window cell = head code + code_d
+    r.green = (r.w == n * W + n) ? 1.0f : 127.0f / 255.0f;
+    r.live_tab = 0;
+#pragma unroll
+    for (int y = 1; y <= 7; ++y) {
+        u32 cols = 0;
+#pragma unroll
+        for (int x = 1; x <= 7; ++x)
+            if ((unsigned)(x + r.dx0 - 1) < 7u) cols |= 1u << x;
+        if ((unsigned)(y + r.dy0 - 1) < 7u) r.live_tab |= (u64)cols << (8 * y);
+    }
+    return r;
+}
+
 // bit (i & 63) of m, for a branch: s_bitcmp1_b64 reads bits [5:0] of its index operand
 __device__ __forceinline__ bool bit_set(u64 m, int i) { return ((m >> (i & 63)) & 1) != 0; }
 

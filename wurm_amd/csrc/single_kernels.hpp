@@ -356,11 +356,14 @@ __global__ __launch_bounds__(256) void rollout_lean_kernel(StepArgs p)
 // PAIR: a workgroup of two waves per env (single_launch.hpp: batches of at most WURM_S9_PAIR_MAX_ENVS envs).  Wave 1 does
 // what a chunk needs around its step loop — tape load, move entries, Philox blocks or recorded outcomes one chunk ahead,
 // the record stores one chunk behind — and wave 0 only steps (DESIGN.md section 4 has the protocol and the measurements).
-template <int OBSK, bool INJ = false, bool PAIR = false>
+// CROPH (with PAIR and partial_n only; single_launch.hpp: launches of at least WURM_S9_CROP_HELPER_MIN_STEPS steps): wave 1
+// also renders the crops, one chunk behind, from what wave 0 records of each step; wave 0's loop holds the transition alone.
+template <int OBSK, bool INJ = false, bool PAIR = false, bool CROPH = false>
 __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
 {
     constexpr int CPL = 2, S = 9;
     static_assert(OBSK == WURM_OBS_PARTIAL || OBSK == WURM_OBS_NONE, "9x9 rollout: partial_n or no observation");
+    static_assert(!CROPH || (PAIR && OBSK == WURM_OBS_PARTIAL), "9x9 rollout: the helper renders the crops of the pair form");
     const int wave = uniform((int)(threadIdx.x >> 6)), wpb = (int)(blockDim.x >> 6);
     // PAIR: one workgroup of two waves per env; both take the next line's exit, or neither
     const long long env = PAIR ? xcd_block(blockIdx.x, gridDim.x) : xcd_block(blockIdx.x, gridDim.x) * wpb + wave;
@@ -438,8 +441,12 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
     // B0 once chunk 0 and the verdict are written, B(k+1) at the end of chunk k.  Between B(k) and B(k+1) the helper writes
     // chunk buffer (k+1) & 1 and reads record buffer (k-1) & 1, the stepper reads chunk buffer k & 1 (at once, into
     // registers) and writes record buffer k & 1 (last).
+    // CROPH: a record buffer is four planes of 64 dwords, the word above and what the crop of step t0 + j is a function of:
+    // head code | (food code + 1) << 7 | move entry bits 4-14 << 14 | collisions << 25, and the two halves of the body mask
+    // without the head.  Between B(k) and B(k+1) the helper also renders chunk k - 1 from record buffer (k-1) & 1 (last, after
+    // the tape load and the record stores); after the last barrier it renders the last chunk.  Same barriers, same parities.
     int *const pair_lds = (int *)(wurm_lds + p.lds_per_wave);
-    constexpr int PAIR_CHUNK = 5 * 64, PAIR_REC = 2 * PAIR_CHUNK, PAIR_LEAN = PAIR_REC + 2 * 64;
+    constexpr int PAIR_CHUNK = 5 * 64, PAIR_REC = 2 * PAIR_CHUNK, PAIR_RECSZ = CROPH ? 4 * 64 : 64, PAIR_LEAN = PAIR_REC + 2 * PAIR_RECSZ;
     const long long n_chunks = (p.T + 63) >> 6;
     if constexpr (PAIR) {
         if (wave != 0) {
@@ -451,8 +458,65 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
             };
             const auto flush_from = [&](const long long k) __attribute__((always_inline)) {
                 const long long t0 = k << 6;
-                const int rec = pair_lds[PAIR_REC + (int)(k & 1) * 64 + lane];
+                const int rec = pair_lds[PAIR_REC + (int)(k & 1) * PAIR_RECSZ + lane];
                 flush(t0, (int)min((long long)64, p.T - t0), (rec << 29) >> 29, (rec >> 3) & 1, rec >> 4);
+            };
+            // CROPH: the crops of chunk k from record buffer k & 1.  The steps are independent: every lane reads its own
+            // step's record, so a window of at most 32 cells renders two steps per pass (lanes 0-31 step j, lanes 32-63
+            // step j + 1; an odd tail renders its last step in both halves: same address, same value).  The head is the
+            // window's centre cell, so `taken` is the body bit or "this lane is the centre"; on an edge collision the head is on
+            // the ring, the centre is outside (shows nothing) and the bit the head would have set aliases ring cells only.
+            // (WURM_S9_CROP_SPP1: a build for tools/kernel_timeline.py that renders one step per pass whatever the window)
+            int spp = 1, sub = 0;
+            S9Window win = {};
+            if constexpr (CROPH) {
+#ifndef WURM_S9_CROP_SPP1
+                spp = (2 * p.obs_n + 1) * (2 * p.obs_n + 1) <= 32 ? 2 : 1;
+#endif
+                sub = spp == 2 ? lane >> 5 : 0;
+                win = s9_window(spp == 2 ? lane & 31 : lane, p.obs_n);
+            }
+            const auto render = [&](const long long k) __attribute__((always_inline)) {
+                const int W2 = (2 * p.obs_n + 1) * (2 * p.obs_n + 1);
+                const long long t0 = k << 6, obs_stride = p.N * p.obs_elems;
+                const int nt = (int)min((long long)64, p.T - t0);
+                const int *rb = pair_lds + PAIR_REC + (int)(k & 1) * PAIR_RECSZ;
+                const int centre = win.code_d == 0 ? 1 : 0, code_d1 = win.code_d + 1;
+                float *obs_t = p.obs + (t0 * p.N + env) * p.obs_elems;
+                const auto pass = [&](const int j, const int my_sub) __attribute__((always_inline)) {
+                    const int sj = j + my_sub;
+                    const int w1 = rb[64 + sj];
+                    const u64 body = (u64)(u32)rb[128 + sj] | ((u64)(u32)rb[192 + sj] << 32);
+                    const int c = w1 & 127;
+                    // (both shifts read the low 6 bits of their amount, which are those of the head code in w1)
+                    unsigned inside = (u32)(win.live_tab >> (w1 & 63)) & 1u;
+                    const bool edge = ((w1 >> 26) & 1) != 0;
+                    if (lane_mask(edge) != 0) {
+                        // the head is on the ring and its code may have wrapped: row / column arithmetic from the cell it left
+                        const int ai = (w1 >> 22) & 3, pc = c - ((w1 << 10) >> 26);
+                        const int hy = (pc >> 3) - tap_y(ai), hx = (pc & 7) - tap_x(ai);
+                        const unsigned e_inside = max((unsigned)(hy + win.dy0 - 1), (unsigned)(hx + win.dx0 - 1)) < 7u ? 1u : 0u;
+                        inside = edge ? e_inside : inside;
+                    }
+                    const unsigned taken = ((u32)(body >> ((w1 + win.code_d) & 63)) & 1u) | (u32)centre;
+                    const unsigned both = inside & taken;
+                    const int code1 = c + code_d1, food1 = (w1 >> 7) & 127; // window cell code + 1, food code + 1 (0: no food)
+                    // as the stepper's crop: vr = inside > taken, vb = code == food ? 0 : vr, vg = inside & taken ? green : vb
+                    const float vr = inside > taken ? 1.0f : 0.0f;
+                    const float vb = code1 != food1 ? vr : 0.0f;
+                    const float vg = both != 0 ? win.green : vb;
+                    const u32 o = (u32)((long long)my_sub * obs_stride * 4) + (u32)win.w * 4u;
+                    // (said outright: the instrumented build loses track of the base being wave-uniform and offers a VGPR pair)
+                    float *const obs_s = (float *)uniform64((long long)obs_t);
+                    asm volatile("global_store_dword %0, %1, %6\n\tglobal_store_dword %2, %3, %6\n\tglobal_store_dword %4, %5, %6"
+                                 : : "v"(o), "v"(vr), "v"(o + (u32)W2 * 4u), "v"(vg), "v"(o + (u32)W2 * 8u), "v"(vb), "s"(obs_s) : "memory");
+                };
+                int j = 0;
+                for (; j + spp <= nt; j += spp) {
+                    pass(j, sub);
+                    obs_t += spp * obs_stride;
+                }
+                if (j < nt) pass(j, 0);
             };
             if (n_chunks > 0) draw_into(0);
             pair_barrier(); // B0
@@ -460,9 +524,22 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
             for (long long k = 0; k < n_chunks; ++k) {
                 if (k + 1 < n_chunks) draw_into(k + 1); // (reads the tape of chunk k + 1 before chunk k - 1 is written back)
                 if (k > 0) flush_from(k - 1);
+                if constexpr (CROPH) {
+                    WURM_TL_LAP(1);
+                    if (k > 0) render(k - 1);
+                    WURM_TL_LAP(2);
+                }
                 pair_barrier(); // B(k+1)
+                if constexpr (CROPH) WURM_TL_LAP(3);
             }
             if (n_chunks > 0) flush_from(n_chunks - 1);
+            if constexpr (CROPH) {
+                WURM_TL_LAP(1);
+                if (n_chunks > 0) render(n_chunks - 1);
+                WURM_TL_LAP(4);
+                // (the helper's laps go over the crop of step 1, the stepper's over that of step 0)
+                if (p.T > 1) WURM_TL_STORE(p.obs + (p.N + env) * p.obs_elems, lane);
+            }
             return;
         }
     }
@@ -548,6 +625,7 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
         }
         // what lane j keeps of step t0 + j: its move entry, whether it ate, self collision | edge collision << 1
         int my_rec = 0, my_ate = 0, my_fl = 0;
+        S9CropRec crop_rec = {0, 0, 0, 0, 0};        // CROPH: what the helper renders step t0 + j's crop from, in lane j
         {   // re-base the clocks so that they cannot overflow however long the tape is
             const int T = T1 - 1;
             ex = max(ex - T, 0);
@@ -567,7 +645,7 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
             // the two words are the halves of one 64-bit table: entry o is bits [16 o, 16 o + 16)
             const u64 mov = (u64)(u32)lane_value(my_mov01, j) | ((u64)(u32)lane_value(my_mov23, j) << 32);
             ent = (int)(u32)(mov >> (ent & 63));     // (the shift reads the low 6 bits of its amount: no instruction)
-            my_rec = set_lane(my_rec, ent, j);       // lane j keeps the record of step t0 + j
+            if constexpr (!CROPH) my_rec = set_lane(my_rec, ent, j); // lane j keeps the record of step t0 + j
             // c += code step: the head is inside the ring, so the move stays on the grid (in place: left to the compiler, the
             // sum lands in a new register and the plain move pays a copy on the back edge)
             asm("s_add_i32 %0, %0, %1" : "+s"(c) : "s"((ent << 20) >> 26) : "scc");
@@ -575,6 +653,8 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
             // T1 += head != food, through the carry: the clock stands still on the step that eats (:242, :246-249), which
             // is the length growing by one
             asm("s_cmp_lg_u32 %1, %2\n\ts_addc_u32 %0, %0, 0" : "+s"(T1) : "s"(c), "s"(foodc) : "scc");
+            // CROPH: the record of a plain move, of a collision and of the reset behind it; a step that eats rewrites its lane below
+            if constexpr (CROPH) set_lane(crop_rec, ent, c, foodc, body_moved, j);
             u64 body = body_moved;
             const u64 head = 1ull << (c & 63);
             ex = keep_in_lane(ex, G, head);          // :258-262 (a head on the ring may land in a wrong lane: it is reset below)
@@ -584,7 +664,7 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
             unsigned inside = 0;
             int code = c + code_d;
             u64 mask = occ;
-            if (OBSK == WURM_OBS_PARTIAL) {
+            if (OBSK == WURM_OBS_PARTIAL && !CROPH) {
                 u64 lv; // live_tab >> head code
                 asm("v_lshrrev_b64 %0, %1, %2" : "=v"(lv) : "s"(c), "v"(live_tab));
                 inside = (u32)lv & 1u;
@@ -617,10 +697,15 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
                         }
                     }
                     XF = RING | (foodc >= 0 ? 1ull << foodc : 0);
+                    if constexpr (CROPH) { // the crop shows the food drawn just now and the body that kept its tail
+                        crop_rec.food = set_lane(crop_rec.food, foodc, j);
+                        crop_rec.body_lo = set_lane(crop_rec.body_lo, (int)(u32)body, j);
+                        crop_rec.body_hi = set_lane(crop_rec.body_hi, (int)(u32)(body >> 32), j);
+                    }
                 }
                 shown_food = foodc;
                 const int event = ((RING >> (c & 63)) & 1) ? 2 : ((body >> (c & 63)) & 1) ? 1 : 0; // self / edge collision
-                if (OBSK == WURM_OBS_PARTIAL && event == 2) {
+                if (OBSK == WURM_OBS_PARTIAL && !CROPH && event == 2) {
                     // the head is on the ring and its code may have wrapped: row / column arithmetic from the cell it left
                     const int ai = (ent >> 12) & 3, pc = c - ((ent << 20) >> 26);
                     const int hy = (pc >> 3) - tap_y(ai), hx = (pc & 7) - tap_x(ai);
@@ -644,8 +729,8 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
 
             // ---- crop of the stepped state (single_snake.py:166-193): a window cell that is off the grid or on the
             // ring is (0,0,0); food (1,0,0), head (0,1,0), body (0,127/255,0), background (1,1,1).  `inside` / `taken`
-            // are 0 / 1 per lane; the class logic stays in the VALU (compare -> select through vcc).
-            if (OBSK == WURM_OBS_PARTIAL) {
+            // are 0 / 1 per lane; the class logic stays in the VALU (compare -> select through vcc).  (CROPH: the helper's.)
+            if (OBSK == WURM_OBS_PARTIAL && !CROPH) {
                 u64 sh; // mask >> code; spelled out: the compiler prefers (1 << code) & mask, two 64-bit VALU ops more
                 asm("v_lshrrev_b64 %0, %1, %2" : "=v"(sh) : "v"(code), "s"(mask));
                 const unsigned taken = (u32)sh & 1u;
@@ -685,14 +770,27 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
         for (; j < nt; ++j) step(j);
         WURM_TL_LAP(3);
         if constexpr (PAIR) {
-            pair_lds[PAIR_REC + (int)((t0 >> 6) & 1) * 64 + lane] = ((my_rec >> 12) & 7) | (my_ate << 3) | (my_fl << 4);
+            if constexpr (CROPH) {
+                // bit fields of the crop word: head code 0-6 (a code is 0 .. 72), food code + 1 7-13 (0 .. 73), move entry
+                // bits 4-14 at 14-24, self / edge collision 25 / 26 (the helper tests bit 26); masked, so that a wider event
+                // code or a negative head code could not spill into a neighbour
+                int *rb = pair_lds + PAIR_REC + (int)((t0 >> 6) & 1) * PAIR_RECSZ + lane;
+                my_rec = crop_rec.ent;
+                rb[64] = (crop_rec.c & 127) | (((crop_rec.food + 1) & 127) << 7) | (((my_rec >> 4) & 0x7FF) << 14) | ((my_fl & 3) << 25);
+                rb[128] = crop_rec.body_lo;
+                rb[192] = crop_rec.body_hi;
+                rb[0] = ((my_rec >> 12) & 7) | (my_ate << 3) | (my_fl << 4);
+            } else {
+                pair_lds[PAIR_REC + (int)((t0 >> 6) & 1) * 64 + lane] = ((my_rec >> 12) & 7) | (my_ate << 3) | (my_fl << 4);
+            }
             pair_barrier(); // B(k+1)
         } else {
             flush(t0, nt, (my_rec << 17) >> 29, my_ate, my_fl);
         }
         WURM_TL_LAP(4);
     }
-    if (OBSK == WURM_OBS_PARTIAL) WURM_TL_STORE(p.obs + env * p.obs_elems, lane);
+    // (CROPH: the helper renders step 0's crop behind the stepper's back while there is one chunk only: no stamps then)
+    if (OBSK == WURM_OBS_PARTIAL && (!CROPH || p.T > 64)) WURM_TL_STORE(p.obs + env * p.obs_elems, lane);
     if (lane_in) { // the ring was empty and still is
         envp[my_cell] = lane == foodc ? 1.0f : 0.0f;
         envp[S * S + my_cell] = lane == c ? 1.0f : 0.0f;

@@ -20,7 +20,8 @@ enum Kind { K_STEP, K_RESET, K_OBSERVE, K_ROLLOUT, K_FUSED };
 //   rollout          | snake, S = 10 / 11, N >= lane_rollout_min_envs, lane_wide_eligible              | R_LANE_WIDE   lane_wide.hpp (default, one_channel, partial_2 / 3, positions, none)
 //   rollout          | snake, S == 9, both inject arrays, partial_n (n <= 3) or none                  | R_S9_INJ      rollout_s9_kernel<., true>
 //   rollout          | snake, S == 9, RNG mode, partial_n (n <= 3) or none                            | R_S9          rollout_s9_kernel
-//                    |   (both rows: N <= s9_pair_max_envs launches the kernel's pair form, two waves per env)
+//                    |   (both rows: N <= s9_pair_max_envs launches the kernel's pair form, two waves per env; with partial_n
+//                    |    and T >= s9_crop_helper_min_steps the form of it whose helper wave renders the crops)
 //   rollout          | snake, S = 10 / 11, RNG mode, partial_n (n <= 3) or none                       | R_LEAN        rollout_lean_kernel
 //   rollout          | snake, S <= 11, RNG mode, partial_n (n <= 6) / none                            | R_GENERIC_PARTIAL / R_GENERIC_NONE (mode as template argument)
 //   rollout          | gridworld, RNG mode, N >= lane_rollout_min_envs, gridworld_lane_eligible        | R_GRIDWORLD_LANE gridworld_lane.hip (+ generic for the rest)
@@ -33,6 +34,8 @@ enum Route { R_GENERIC, R_GRID_STEP, R_LANE_STEP, R_GRID_ROLLOUT, R_LANE_ROLLOUT
 extern thread_local Route last_route;
 // (wurm_single_last_waves_per_env: 2 if that launch was rollout_s9_kernel's pair form, else 1)
 extern thread_local int last_waves_per_env;
+// (wurm_single_last_crop_wave: 1 if that launch was the pair form whose helper wave renders the crops, else 0)
+extern thread_local int last_crop_wave;
 
 static const char *route_name(Route r)
 {
@@ -85,6 +88,7 @@ static hipError_t launch_one(Kind kind, const StepArgs &p, dim3 grid, dim3 block
     const Route route = route_of(kind, SNAKE, CPL, p);
     last_route = route;
     last_waves_per_env = 1;
+    last_crop_wave = 0;
     // (the one-env-per-wave code behind a grid / lane kernel, for the envs that one could not take: flagged_kernel, a wave per 64 envs)
     const unsigned wpb_f = block.x / 64u;
     const dim3 fgrid((unsigned)((p.N + 64ll * wpb_f - 1) / (64ll * wpb_f)));
@@ -142,6 +146,16 @@ static hipError_t launch_one(Kind kind, const StepArgs &p, dim3 grid, dim3 block
                 const dim3 pgrid((unsigned)p.N), pblock(128);
                 const size_t plds = (size_t)p.lds_per_wave + (2 * 5 * 64 + 2 * 64 + 4) * sizeof(int);
                 last_waves_per_env = 2;
+                // The helper renders the crops too where the launch is long enough for that to pay (the last chunk is
+                // rendered after the stepper has finished): record buffers of 4 x 64 dwords.  (Its lanes address the second
+                // step of a pass by a 32-bit byte offset of one step's observations.)
+                if (!none && opt.s9_crop_helper_min_steps >= 0 && p.T >= opt.s9_crop_helper_min_steps &&
+                    p.N * p.obs_elems * 4 < (1ll << 31)) {
+                    const size_t clds = (size_t)p.lds_per_wave + (2 * 5 * 64 + 2 * 4 * 64 + 4) * sizeof(int);
+                    last_crop_wave = 1;
+                    if (inj) WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_PARTIAL, true, true, true>), pgrid, pblock, clds, st, p);
+                    else WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_PARTIAL, false, true, true>), pgrid, pblock, clds, st, p);
+                } else
                 if (inj && none) WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_NONE, true, true>), pgrid, pblock, plds, st, p);
                 else if (inj) WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_PARTIAL, true, true>), pgrid, pblock, plds, st, p);
                 else if (none) WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_NONE, false, true>), pgrid, pblock, plds, st, p);

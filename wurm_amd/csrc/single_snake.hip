@@ -7,6 +7,7 @@ namespace wurm {
 
 thread_local Route last_route = R_GENERIC;
 thread_local int last_waves_per_env = 1;
+thread_local int last_crop_wave = 0;
 
 template int launch<true>(Kind, StepArgs, void *);
 extern template int launch<false>(Kind, StepArgs, void *); // single_grid.hip
@@ -200,6 +201,7 @@ extern "C" {
 
 const char *wurm_version(void) { return "wurm_hip 0.1 gfx950"; }
 const char *wurm_single_last_route(void) { return route_name(last_route); }
+int wurm_single_last_crop_wave(void) { return (last_route == R_S9 || last_route == R_S9_INJ) ? last_crop_wave : 0; }
 int wurm_single_last_waves_per_env(void) { return (last_route == R_S9 || last_route == R_S9_INJ) ? last_waves_per_env : 1; }
 
 int64_t wurm_single_obs_elems(int obs_mode, int obs_n, int size) { return obs_elems(true, obs_mode, obs_n, size); }

@@ -1,7 +1,8 @@
 """Multi-agent A2C with a feed-forward policy per species, on this project's HIP paths end to end: the acting loop of the
 reference's experiments/multiagent.py:350-378 is `MultiSnake.act_window` (two launches per step: one `act` for every
 snake of every species, one `step` with the postponed reset), the learners are one `FusedA2CPopulation` with a member per
-species (three launches per window).
+species (three launches per window), the log columns of multiagent.py:486-505 are kept on the device by
+`MultiRolloutStats` (two launches per window; copied to the host only when a line is printed).
 
     python examples/a2c_multi_species.py --num-envs 512 --n-agents 4 --n-species 2 --total-steps 200000
     python examples/a2c_multi_species.py --num-envs 8 --n-agents 2 --n-species 2 --size 12 --total-steps 640   # tiny
@@ -18,7 +19,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from wurm_amd.agents import FeedforwardAgent  # noqa: E402
 from wurm_amd.envs import MultiSnake  # noqa: E402
-from wurm_amd.rl import FusedA2CPopulation  # noqa: E402
+from wurm_amd.rl import FusedA2CPopulation, MultiRolloutStats  # noqa: E402
 
 
 def main(argv=None):
@@ -44,23 +45,29 @@ def main(argv=None):
                      boost=False, food_mode='random_rate', respawn_mode='any', seed=args.seed)
     agents = [FeedforwardAgent(num_actions=4, num_layers=2, hidden_units=64, num_inputs=E).to(env.device) for _ in range(P)]
     learner = FusedA2CPopulation(agents, lr=args.lr, gamma=args.gamma, entropy_coef=args.entropy)
+    stats = MultiRolloutStats(env)
     state = env.reset()
     steps, window = 0, 0
     while steps < args.total_steps:
-        out = env.act_window(learner.params, state, T)
+        out = env.act_window(learner.params, state, T, info=True)
         x0 = torch.stack(list(state.values())).reshape(K * N, E)
         res = learner.update(x0, out)
+        stats.update(out)
         state = out['state']
         steps += T * N
         window += 1
         if window % 10 == 1 or steps >= args.total_steps:
-            # per species, from the window tensors: a species owns the columns [s K/P N, (s + 1) K/P N)
-            reward = out['rewards'].view(T, P, -1).mean(dim=(0, 2)).tolist()
-            done = out['dones'].view(T, P, -1).float().mean(dim=(0, 2)).tolist()
-            vl, ent = res['value_loss'].tolist(), res['entropy'].tolist()
-            print(f'steps {steps:9d} | ' + ' | '.join(
-                f'species {s}: reward {reward[s]:+.4f} done {done[s]:.4f} value loss {vl[s]:.4f} entropy {ent[s]:.3f}'
-                for s in range(P)), flush=True)
+            # since the last line: agent 0's columns (smoothed, as the reference prints them) and each species' means
+            species = stats.read(reset=False, num_species=P)
+            a = stats.read()[0]
+            vl = res['value_loss'].tolist()
+            print(f'steps {steps:9d} episodes {a["episodes"]:6d} | agent 0: Reward {a["ewm_reward"]:+.2e} Food '
+                  f'{a["ewm_food"]:.2e} Entropy {a["ewm_policy_entropy"]:.2e} Done {a["ewm_done"]:.2e} Edge '
+                  f'{a["ewm_edge_collisions"]:.2e} Collision {a["ewm_snake_collisions"]:.2e} Size {a["ewm_size"]:.3f} '
+                  f'Return {a["ewm_return"]:.3f} | ' + ' | '.join(
+                      f'species {s}: reward {r["reward"]:+.4f} done {r["done"]:.4f} size {r["size"]:.3f} life '
+                      f'{r["life_length_mean"]:.1f} value loss {vl[s]:.4f} entropy {r["policy_entropy"]:.3f}'
+                      for s, r in enumerate(species)), flush=True)
     return learner
 
 

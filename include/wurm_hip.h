@@ -824,6 +824,51 @@ int wurm_rollout_stats(const float *rewards, const uint8_t *dones, const uint8_t
                        double *table, void *workspace, int64_t workspace_bytes, int64_t num_envs, int64_t num_steps,
                        int64_t num_members, int initial_size, double alpha, void *stream);
 
+/* ---- the multi-agent log columns (wurm_amd/csrc/multi_rollout_stats.hpp) -----------------------------------------------
+ * The per-agent columns of experiments/multiagent.py:486-505 (reward_i, policy_entropy_i, food_i, edge_collisions_i,
+ * snake_collisions_i, boost_i, size_i, done_i, return_i, their ExponentialMovingAverageTracker versions, episodes) from the
+ * (T, K N) outputs of a MultiSnake window (MultiSnake.act_window(..., info=True) or MultiSnake.rollout), carried from
+ * window to window: two launches (a scan and a reduce), no host synchronisation, no atomics, no scratch (bit-identical
+ * from run to run).  A row is one (snake k, env i) pair, column k N + i, N = num_envs, K = num_snakes.
+ *   rewards, food, size (T, K N) fp32 (size is a snake's length: an integer, read as one);  dones, boost,
+ *   snake_collision, edge_collision (T, K N) bytes;  probs (T, K N, 4) fp32, 16-byte aligned, nullable (H = 0);
+ *   all_done (T, N) bytes, nullable (episodes stays 0).
+ *   H = - sum_k p_k log(clamp(p_k, eps32, 1 - eps32)) in fp32, the learner's expression (wurm_rollout_stats above).
+ *   With alive = !done, the ten batch sums over the N envs of agent k at step t, in this order: [0] alive, [1] done,
+ *   [2] reward alive, [3] H alive, [4] food alive, [5] boost alive, [6] size alive, [7] edge_collision,
+ *   [8] snake_collision, [9] size done.  All but [2], [3] and [4] are sums of integers: exact.
+ *   Per step and row: life_return += reward, life_length += 1; on every step where done is set the pair joins the agent's
+ *   sums over deaths, feeds the maximum of the life return beside the size at death, and is cleared.  A snake that stays
+ *   done for several steps counts on each of them, as the reference's size_i[done_i] column does.
+ * carry    (2, K N) 4-byte words, read and written: row 0 life_return (fp32), row 1 life_length (int32).  Zeros at first.
+ * accum    (K, 16) doubles, added to: [0] env steps (T N per call), [1..10] the ten sums over the window's steps,
+ *          [11] the sum of life_return over deaths, [12] of life_length, the maxima of [13] size at death and [14]
+ *          life_return over deaths, folded in with fmax (the caller initialises the two to -infinity), [15] episodes =
+ *          the sum of all_done over the window, the same number in every agent's row.
+ * table    nullable, (K, T, 10) doubles, written: the ten sums of step t.
+ * smooth   (K, 9) doubles, read and written: ExponentialMovingAverageTracker(alpha) (wurm/utils.py:323-337) in step
+ *          order, in double, over the per-step values reward [2]/[0], policy_entropy [3]/[0], food [4]/[0],
+ *          edge_collisions [7]/N, snake_collisions [8]/N, boost [5]/[0], size [6]/[0], done [1]/N, return [9]/[1]: a NaN
+ *          entry is "nothing seen yet" and takes the first value; after that s = alpha x + (1 - alpha) s.  The caller
+ *          initialises it to NaN.  DEVIATION: a step whose mask is empty ([0] or [1] is 0) gives the reference a NaN mean
+ *          that its tracker never recovers from (return_i on the first step without a death); here such a step leaves
+ *          that column's smoother as it was.
+ * Agent k owns row k of accum, table and smooth; its numbers are bit for bit those of a call with num_snakes = 1 on
+ * contiguous copies of its N columns.
+ * Refused before any HIP call: a null required pointer, num_envs <= 0, num_snakes <= 0, num_steps <= 0, alpha outside
+ * [0, 1], a workspace that is too small or not 16-byte aligned, probs not 16-byte aligned (WURM_ERR_INVALID_ARG); more
+ * than 65535 snakes (WURM_ERR_UNSUPPORTED). */
+
+/* Bytes of the caller-owned workspace (0 for arguments the call refuses): 10 T + 5 doubles per wave of 64 envs of an agent
+ * (four to a workgroup), and the per-step sums. */
+int64_t wurm_multi_rollout_stats_workspace_bytes(int64_t num_envs, int64_t num_snakes, int64_t num_steps);
+
+int wurm_multi_rollout_stats(const float *rewards, const float *food, const float *size, const uint8_t *dones,
+                             const uint8_t *boost, const uint8_t *snake_collision, const uint8_t *edge_collision,
+                             const float *probs, const uint8_t *all_done, void *carry, double *accum, double *smooth,
+                             double *table, void *workspace, int64_t workspace_bytes, int64_t num_envs,
+                             int64_t num_snakes, int64_t num_steps, double alpha, void *stream);
+
 /* ---- frames of a fused window, after the fact (wurm_amd/csrc/rollout_frames.hpp) --------------------------------------
  * A window of wurm_single_rollout / wurm_*_policy_rollout* (and the SimpleGridworld forms) is a pure function of an env's
  * start state, its id env_offset + index, seed, the window's first call counter call0 and the SANITISED actions the launch

@@ -53,6 +53,19 @@ __device__ __forceinline__ double wave_max_f64(double v)
     return v;
 }
 
+// H = - sum_k p_k log(clamp(p_k, eps32, 1 - eps32)) in fp32: the learner's expression (a2c_learner.hpp)
+__device__ __forceinline__ float entropy_f32(const float4 p4)
+{
+    const float eps32 = 1.1920928955078125e-07f, hi32 = 1.0f - eps32;
+    const float p[4] = {p4.x, p4.y, p4.z, p4.w};
+    float h = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) h -= p[k] * logf(fminf(fmaxf(p[k], eps32), hi32));
+    return h;
+}
+
+#ifndef WURM_STATS_HELPERS_ONLY // (multi_rollout_stats.hpp includes this header for what is above, not for the kernels)
+
 // member blockIdx.y, envs [m M, (m + 1) M): workgroup blockIdx.x of the member has its envs [256 x, 256 x + 256), the
 // waves and lanes of a stand-alone call on the member's M columns
 __global__ __launch_bounds__(THREADS) void rollout_stats_scan_kernel(scan_args g)
@@ -72,7 +85,6 @@ __global__ __launch_bounds__(THREADS) void rollout_stats_scan_kernel(scan_args g
         size = g.carry_size[env];
     }
     double ep_ret = 0.0, ep_len = 0.0, ep_size = 0.0, max_ret = -INFINITY, max_size = -INFINITY; // no episode yet
-    const float eps32 = 1.1920928955078125e-07f, hi32 = 1.0f - eps32;
 
     for (long long t = 0; t < g.T; ++t) {
         double c[COLS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -99,14 +111,7 @@ __global__ __launch_bounds__(THREADS) void rollout_stats_scan_kernel(scan_args g
             c[2] = g.edge[i] ? 1.0 : 0.0;
             c[3] = g.self && g.self[i] ? 1.0 : 0.0;
             c[4] = (double)size;
-            if (g.probs) {
-                const float4 p4 = *reinterpret_cast<const float4 *>(g.probs + 4 * i);
-                const float p[4] = {p4.x, p4.y, p4.z, p4.w};
-                float h = 0.0f; // the learner's expression (a2c_learner.hpp)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) h -= p[k] * logf(fminf(fmaxf(p[k], eps32), hi32));
-                c[5] = (double)h;
-            }
+            if (g.probs) c[5] = (double)entropy_f32(*reinterpret_cast<const float4 *>(g.probs + 4 * i));
         }
         double (*buf)[COLS] = sums[t & 1]; // two buffers: one barrier per step
 #pragma unroll
@@ -192,6 +197,8 @@ __global__ __launch_bounds__(THREADS) void rollout_stats_reduce_kernel(const dou
         accum[tid] = fmax(accum[tid], window[tid - (COLS + 1)]); // (-inf: no episode has ended yet)
     }
 }
+
+#endif // WURM_STATS_HELPERS_ONLY
 
 } // namespace stats
 } // namespace wurm

@@ -155,7 +155,12 @@ def act(env, params, observations, num_species=None, out=None) -> dict:
             'values': values}
 
 
-def act_window(env, params, state, num_steps, num_species=None) -> dict:
+# the keys `act_window(..., info=True)` adds: (name, prefix of the step's info key, dtype)
+INFO_KEYS = (('food', 'food_', torch.float32), ('size', 'size_', torch.float32), ('boost', 'boost_', torch.bool),
+             ('snake_collision', 'snake_collision_', torch.bool), ('edge_collision', 'edge_collision_', torch.bool))
+
+
+def act_window(env, params, state, num_steps, num_species=None, info=False) -> dict:
     """MultiSnake.act_window"""
     T, K, N, dev = int(num_steps), env.num_snakes, env.num_envs, env.device
     if T < 0:
@@ -165,11 +170,13 @@ def act_window(env, params, state, num_steps, num_species=None) -> dict:
     probs = torch.empty((T, K * N, 4), dtype=torch.float32, device=dev)
     values = torch.empty((T, K * N), dtype=torch.float32, device=dev)
     keys = [f'agent_{k}' for k in range(K)]
-    obs_rows, reward_rows, done_rows, all_rows = [], [], [], []
+    obs_rows, reward_rows, done_rows, all_rows, infos = [], [], [], [], []
     for t in range(T):
         a = act(env, params, state, num_species, (actions[t].view(K, N), probs[t].view(K, N, 4), values[t].view(K, N)))
-        obs, rewards, dones, _ = env.step(a['actions'])
+        obs, rewards, dones, step_info = env.step(a['actions'])
         env.reset(dones['__all__'], return_observations=False)
+        if info:
+            infos.append(step_info)  # (a dict over the step's output slab that carves its rows when it is read, below)
         # (views of the step's own output slab: gathered once, behind the loop)
         obs_rows.extend(obs[k] for k in keys)
         reward_rows.extend(rewards[k] for k in keys)
@@ -187,5 +194,12 @@ def act_window(env, params, state, num_steps, num_species=None) -> dict:
         rewards_t = torch.stack(reward_rows).view(T, K * N)
         dones_t = torch.stack(done_rows).view(T, K * N)
         all_done = torch.stack(all_rows)
-    return {'observations': observations, 'actions': actions, 'probs': probs, 'values': values, 'rewards': rewards_t,
-            'dones': dones_t, 'all_done': all_done, 'state': state}
+    out = {'observations': observations, 'actions': actions, 'probs': probs, 'values': values, 'rewards': rewards_t,
+           'dones': dones_t, 'all_done': all_done, 'state': state}
+    if info:  # what `step` logged per agent (reference :707-729), gathered like rewards and dones: one stack per key
+        for name, prefix, dtype in INFO_KEYS:
+            if T == 0:
+                out[name] = torch.empty((0, K * N), dtype=dtype, device=dev)
+            else:
+                out[name] = torch.stack([i[f'{prefix}{k}'] for i in infos for k in range(K)]).view(T, K * N)
+    return out

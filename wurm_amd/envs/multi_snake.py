@@ -867,7 +867,8 @@ class MultiSnake(object):
         from wurm_amd.envs import _multi_act
         return _multi_act.act(self, params, observations, num_species)
 
-    def act_window(self, params: torch.Tensor, state, num_steps: int, num_species: int = None) -> dict:
+    def act_window(self, params: torch.Tensor, state, num_steps: int, num_species: int = None,
+                   info: bool = False) -> dict:
         """`num_steps` iterations of the reference's acting loop (experiments/multiagent.py:354-378)
             a = act(params, state); obs, r, d, info = step(a['actions']); reset(d['__all__'], return_observations=False);
             state = obs
@@ -876,9 +877,11 @@ class MultiSnake(object):
         `rewards`, `dones` (T, K N), `all_done` (T, N), and `state`, the last observations.  With one species per equal
         block of snakes this is what `FusedA2CPopulation.update(state0.reshape(K N, E), out)` takes, one member per
         species.  `actions`, `probs` and `values` are allocated once and written in place by `act`; what `step` returns
-        lives in its output slab and is gathered once behind the loop."""
+        lives in its output slab and is gathered once behind the loop.  info=True also gathers what `step` put into its
+        `info` dict, under the names of `rollout`: `food`, `size` (T, K N) fp32, `boost`, `snake_collision`,
+        `edge_collision` (T, K N) bool — what `wurm_amd.rl.MultiRolloutStats.update` takes; no launch more."""
         from wurm_amd.envs import _multi_act
-        return _multi_act.act_window(self, params, state, num_steps, num_species)
+        return _multi_act.act_window(self, params, state, num_steps, num_species, info)
 
     # ------------------------------------------------------------------ invariants
 

@@ -81,13 +81,15 @@ int64_t wurm_launch_count(void);
 const char *wurm_single_last_route(void);
 
 /* Waves per env of that launch: 2 if it was rollout_s9_kernel's pair form ("rollout_s9" / "rollout_s9_injected" with at most
- * WURM_S9_PAIR_MAX_ENVS envs, default 1024: a workgroup of a stepping wave and a helper wave per env; 0 = never), else 1.
+ * WURM_S9_PAIR_MAX_ENVS envs, default 1024: a workgroup of a stepping wave and a helper wave per env; 0 = never), 3 if it was
+ * that kernel's trio form (where the helper wave would render the crops, see below: at most WURM_S9_TRIO_MAX_ENVS envs, default
+ * 512, and at least WURM_S9_TRIO_MIN_STEPS steps, default 512, -1 = never: a second render wave beside the helper), else 1.
  * Results do not depend on the form.  Diagnostic only (tests/test_s9_pair_rollout.py tells the two forms apart by it). */
 int wurm_single_last_waves_per_env(void);
 
 /* Which wave of that launch rendered the partial_n crops: 1 if it was the pair form whose helper wave renders them (the pair
  * form above, partial_n, at least WURM_S9_CROP_HELPER_MIN_STEPS steps, default 256; -1 = never), else 0: the stepping wave,
- * or a kernel without that split.  Results do not depend on it.  Diagnostic only (tests/test_s9_crop_helper.py). */
+ * or a kernel without that split; in the trio form wave 2 renders beside wave 1, and this stays 1.  Results do not depend on it.  Diagnostic only (tests/test_s9_crop_helper.py). */
 int wurm_single_last_crop_wave(void);
 
 /* The same for MultiSnake: the kernel instantiation that served the calling thread's last wurm_multi_* launch, by its row in

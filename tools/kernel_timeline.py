@@ -5,7 +5,7 @@ Needs the instrumented build of the library (s_memtime stamps, wurm_amd/csrc/wur
     make -C wurm_amd/csrc timeline          # -> wurm_amd/libwurm_hip_timeline.so (cross-compiles without a GPU)
     WURM_HIP_LIBRARY=$PWD/wurm_amd/libwurm_hip_timeline.so python tools/kernel_timeline.py [--kernel resident|lane_step]
                                                             [--envs 65536] [--epw 32] [--form ref|noobs]
-    ... python tools/kernel_timeline.py --kernel s9 [--envs 512] [--steps 1024] [--pair 0|1] [--crop-helper 0|1]
+    ... python tools/kernel_timeline.py --kernel s9 [--envs 512] [--steps 1024] [--pair 0|1] [--crop-helper 0|1] [--render-waves 1|2]
 Every wave overwrites the first 64 bytes of its own observation block with eight stamps once its stores have drained; this
 script reads them back from the observation `step` returned and prints, per segment between two stamps, the distribution
 over the waves in s_memtime ticks — counters of different XCDs are not synchronised, so only differences within one wave
@@ -16,7 +16,9 @@ launch), one wave form (--pair 0) or pair form (--pair 1).  Its stamps are TOTAL
 --crop-helper 1 (with --pair 1, --steps above 64): the pair form whose helper wave renders the crops; the helper's own laps,
 which it leaves over the crop of step 1, are printed too: its rendering time per chunk against the stepper's stepping time
 per chunk, and what each wave waits at the chunk barrier.  (A library built with -DWURM_S9_CROP_SPP1 as well renders one
-step per pass whatever the window: the measurement the two-steps-per-pass renderer rests on.)"""
+step per pass whatever the window: the measurement the two-steps-per-pass renderer rests on.)
+--render-waves 2 (with --crop-helper 1, --steps above 128): the trio form, whose wave 2 renders most of each chunk beside the
+helper; wave 2 leaves its laps over the crop of step 2 and gets a section of its own."""
 import argparse
 import os
 import sys
@@ -32,6 +34,7 @@ ap.add_argument('--iters', type=int, default=12)
 ap.add_argument('--steps', type=int, default=1024, help='--kernel s9: batch-steps per launch')
 ap.add_argument('--pair', type=int, default=0, choices=[0, 1], help='--kernel s9: the pair form (two waves per env)')
 ap.add_argument('--crop-helper', type=int, default=0, choices=[0, 1], help='--kernel s9 --pair 1: the helper wave renders the crops')
+ap.add_argument('--render-waves', type=int, default=1, choices=[1, 2], help='--kernel s9 --crop-helper 1: 2 = the trio form, a second render wave')
 args = ap.parse_args()
 if 'timeline' not in os.environ.get('WURM_HIP_LIBRARY', ''):
     sys.exit('set WURM_HIP_LIBRARY to the instrumented library (see the docstring)')
@@ -54,24 +57,29 @@ def s9_timeline():
     env = SingleSnake(num_envs=N_, size=9, observation_mode='partial_2', device='cuda', seed=0)
     _lib.set_option('WURM_S9_PAIR_MAX_ENVS', (1 << 40) if args.pair else 0)
     _lib.set_option('WURM_S9_CROP_HELPER_MIN_STEPS', 1 if args.crop_helper else -1)
+    _lib.set_option('WURM_S9_TRIO_MAX_ENVS', 1 << 40)
+    _lib.set_option('WURM_S9_TRIO_MIN_STEPS', 1 if args.render_waves == 2 else -1)
     assert not args.crop_helper or (args.pair and T > 64), '--crop-helper 1 needs --pair 1 and more than one chunk'
-    helper_rows = []
+    assert args.render_waves == 1 or (args.crop_helper and T > 128), '--render-waves 2 needs --crop-helper 1 and more than two chunks'
+    helper_rows, wave2_rows = [], []
     g = torch.Generator(device='cuda').manual_seed(1)
     rows = []
     for it in range(args.iters):
         out = env.rollout(torch.randint(0, 4, (T, N_), device='cuda', generator=g))
         torch.cuda.synchronize()
-        assert _lib.lib().wurm_single_last_waves_per_env() == 1 + args.pair
+        assert _lib.lib().wurm_single_last_waves_per_env() == (3 if args.render_waves == 2 else 1 + args.pair)
         assert _lib.lib().wurm_single_last_crop_wave() == args.crop_helper
         obs = out['observations']
         if it >= 4:
             rows.append(obs[0].reshape(N_, -1)[:, :16].contiguous().view(torch.int64).cpu().numpy().astype(np.int64))
             if args.crop_helper:
                 helper_rows.append(obs[1].reshape(N_, -1)[:, :16].contiguous().view(torch.int64).cpu().numpy().astype(np.int64))
+            if args.render_waves == 2:
+                wave2_rows.append(obs[2].reshape(N_, -1)[:, :16].contiguous().view(torch.int64).cpu().numpy().astype(np.int64))
     st = np.concatenate(rows)
     life = st[:, 7] - st[:, 0]
     st, life = st[(life > 0) & (life < 10 ** 9)], life[(life > 0) & (life < 10 ** 9)]
-    form = 'pair form, crops by the helper' if args.crop_helper else 'pair form' if args.pair else 'one-wave form'
+    form = 'trio form, crops by the helper and wave 2' if args.render_waves == 2 else 'pair form, crops by the helper' if args.crop_helper else 'pair form' if args.pair else 'one-wave form'
     print(f'rollout_s9_kernel, {N_} envs x {T} steps, {form}: {len(life)} stepper samples; '
           f's_memtime ticks, totals over {(T + 63) // 64} chunks')
     named = [(5, 'state load + setup'), (1, 'wait for the chunk inputs'), (2, 'prologue arithmetic'), (3, 'step loop'),
@@ -103,6 +111,23 @@ def s9_timeline():
           f'{int(np.median(hs[:, 2])) // max(C - 1, 1)} and does its other work in {int(np.median(hs[:, 1])) // C}; '
           f'the stepper\'s hand-over and barrier wait is {100.0 * np.median(st[:, 4]) / np.median(life):.1f} % of its life, '
           f'the helper\'s barrier wait {100.0 * np.median(hs[:, 3]) / np.median(hl):.1f} % of its own')
+    print(f'stepper\'s hand-over and barrier wait: p50 {int(np.median(st[:, 4]))}  p90 {int(np.percentile(st[:, 4], 90))} ticks; '
+          f'last chunk after the stepper has finished: helper p50 {int(np.median(hs[:, 4]))}  p90 {int(np.percentile(hs[:, 4], 90))}')
+    if args.render_waves != 2:
+        return
+    ws = np.concatenate(wave2_rows)
+    wl = ws[:, 7] - ws[:, 0]
+    ws, wl = ws[(wl > 0) & (wl < 10 ** 9)], wl[(wl > 0) & (wl < 10 ** 9)]
+    print(f'wave 2 (renders only): {len(wl)} samples')
+    for k, name in [(1, 'B0 and loop overhead'), (2, 'rendering, chunks 0 .. C-2'), (3, 'wait at the chunk barrier'),
+                    (4, 'rendering, last chunk')]:
+        c = ws[:, k]
+        print(f'  {name:>26s} p10 {int(np.percentile(c, 10)):7d}  p50 {int(np.median(c)):7d}  p90 {int(np.percentile(c, 90)):7d}  '
+              f'max {int(c.max()):7d}   {100.0 * np.median(c) / np.median(wl):5.1f} % of p50 life')
+    print(f'  wave lifetime: p10 {int(np.percentile(wl, 10))}  p50 {int(np.median(wl))}  p90 {int(np.percentile(wl, 90))}  max {int(wl.max())}')
+    print(f'per chunk, p50: wave 2 renders {int(np.median(ws[:, 2])) // max(C - 1, 1)} ticks and waits at the barrier '
+          f'{int(np.median(ws[:, 3])) // C}; the helper renders and works {(int(np.median(hs[:, 2])) + int(np.median(hs[:, 1]))) // C} '
+          f'and waits {int(np.median(hs[:, 3])) // C}; the stepper steps {int(np.median(st[:, 3])) // C}')
 
 
 if args.kernel == 's9':

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""rollout_s9_kernel, pair form against one-wave form by batch size (SingleSnake N x 9 x 9 'partial_2', T batch-steps per
-launch): one process, the same env object and buffers, the form switched by WURM_S9_PAIR_MAX_ENVS between rounds that
-alternate.  Per N and form: the rounds' times per launch (each round the mean of --launches launches between two events),
-their median and spread (max - min over the median); the pair form "wins" at N if its slowest round beats the one-wave
-form's fastest by more than the larger spread.  Prints one JSON document.
+"""rollout_s9_kernel, pair form against one-wave form, and trio form (a second render wave) against pair form, by batch size
+(SingleSnake N x 9 x 9 'partial_2', T batch-steps per launch): one process, the same env object and buffers, the form switched
+by WURM_S9_PAIR_MAX_ENVS and WURM_S9_TRIO_MIN_STEPS between rounds that alternate.  Per N and form: the rounds' times per
+launch (each round the mean of --launches launches between two events), their median and spread (max - min over the
+median); the pair form "wins" at N if its slowest round beats the one-wave form's fastest by more than the larger spread,
+the trio form if its slowest round beats the pair form's fastest likewise.  (The trio form exists where the helper renders
+the crops: --steps at least WURM_S9_CROP_HELPER_MIN_STEPS.)  Prints one JSON document.
     python tools/s9_pair_by_envs.py [--envs 128,256,512,1024,2048,4096] [--steps 1024] [--rounds 5] [--launches 10]"""
 import argparse
 import json
@@ -21,16 +23,18 @@ ap.add_argument('--steps', type=int, default=1024)
 ap.add_argument('--rounds', type=int, default=5)
 ap.add_argument('--launches', type=int, default=10)
 args = ap.parse_args()
-KNOB = 'WURM_S9_PAIR_MAX_ENVS'
+KNOB, TRIO_KNOB = 'WURM_S9_PAIR_MAX_ENVS', 'WURM_S9_TRIO_MIN_STEPS'
+_lib.set_option('WURM_S9_TRIO_MAX_ENVS', 1 << 40)
 dev = torch.device('cuda:0')
 rows = []
 for N in [int(v) for v in args.envs.split(',')]:
     env = SingleSnake(num_envs=N, size=9, observation_mode='partial_2', device=dev, seed=0)
     actions = torch.randint(4, (args.steps, N), device=dev, dtype=torch.int64)
-    times = {1: [], 2: []}
+    times = {1: [], 2: [], 3: []}
     for r in range(args.rounds + 1):        # (round 0 warms both forms up)
-        for waves in (1, 2):
+        for waves in (1, 2, 3):
             _lib.set_option(KNOB, 0 if waves == 1 else 1 << 40)
+            _lib.set_option(TRIO_KNOB, 1 if waves == 3 else -1)
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record()
             for _ in range(args.launches):
@@ -41,7 +45,7 @@ for N in [int(v) for v in args.envs.split(',')]:
             if r > 0:
                 times[waves].append(t0.elapsed_time(t1) / args.launches)
     row = {'envs': N, 'steps': args.steps}
-    for waves, name in ((1, 'one_wave'), (2, 'pair')):
+    for waves, name in ((1, 'one_wave'), (2, 'pair'), (3, 'trio')):
         ts = sorted(times[waves])
         med = ts[len(ts) // 2]
         row[name] = {'ms_per_launch': [round(t, 5) for t in times[waves]], 'median_ms': round(med, 5),
@@ -51,10 +55,19 @@ for N in [int(v) for v in args.envs.split(',')]:
     row['gain_worst_case'] = round(gain, 5)
     row['gain_median'] = round(row['one_wave']['median_ms'] / row['pair']['median_ms'] - 1.0, 5)
     row['pair_wins'] = bool(gain > spread)
+    trio_spread = max(row['pair']['spread'], row['trio']['spread'])
+    trio_gain = min(times[2]) / max(times[3]) - 1.0     # slowest trio round over fastest pair round
+    row['trio_gain_worst_case'] = round(trio_gain, 5)
+    row['trio_gain_median'] = round(row['pair']['median_ms'] / row['trio']['median_ms'] - 1.0, 5)
+    row['trio_wins'] = bool(trio_gain > trio_spread)
     rows.append(row)
     print(f"# N {N:5d}: one wave {row['one_wave']['median_ms']:.4f} ms  pair {row['pair']['median_ms']:.4f} ms  "
-          f"gain {100 * row['gain_median']:+.2f} % (worst case {100 * gain:+.2f} %, spread {100 * spread:.2f} %)", file=sys.stderr, flush=True)
+          f"gain {100 * row['gain_median']:+.2f} % (worst case {100 * gain:+.2f} %, spread {100 * spread:.2f} %)  "
+          f"trio {row['trio']['median_ms']:.4f} ms  gain over pair {100 * row['trio_gain_median']:+.2f} % (worst case {100 * trio_gain:+.2f} %, "
+          f"spread {100 * trio_spread:.2f} %)", file=sys.stderr, flush=True)
     del env, actions
-_lib.set_option(KNOB, None)
+for k in (KNOB, TRIO_KNOB, 'WURM_S9_TRIO_MAX_ENVS'):
+    _lib.set_option(k, None)
 print(json.dumps({'kernel': 'rollout_s9_kernel<partial>', 'rounds': args.rounds, 'launches_per_round': args.launches,
-                  'default_' + KNOB: _lib.get_option(KNOB), 'rows': rows}, indent=1))
+                  'default_' + KNOB: _lib.get_option(KNOB),
+                  'default_WURM_S9_TRIO_MAX_ENVS': _lib.get_option('WURM_S9_TRIO_MAX_ENVS'), 'rows': rows}, indent=1))

@@ -10,7 +10,7 @@
 
 namespace wurm {
 
-constexpr Options DEFAULTS = {1ll << 20, 12288, 6144, -1, -1, -1, 12, 0, 2048, 0, -1, 0, 0, 1, -1, -1, 0, 1024, 256};
+constexpr Options DEFAULTS = {1ll << 20, 12288, 6144, -1, -1, -1, 12, 0, 2048, 0, -1, 0, 0, 1, -1, -1, 0, 1024, 256, 512, 512};
 // PROCESS-WIDE: every env object and every thread of the process sees the same knobs (documented in include/wurm_hip.h);
 // the launch counter is a diagnostic that concurrent launchers may bump at the same time, hence atomic.
 Options opt = DEFAULTS;
@@ -43,6 +43,8 @@ const Entry table[] = {
     {"WURM_POLICY_WIDE", &Options::policy_wide},
     {"WURM_S9_PAIR_MAX_ENVS", &Options::s9_pair_max_envs},
     {"WURM_S9_CROP_HELPER_MIN_STEPS", &Options::s9_crop_helper_min_steps},
+    {"WURM_S9_TRIO_MAX_ENVS", &Options::s9_trio_max_envs},
+    {"WURM_S9_TRIO_MIN_STEPS", &Options::s9_trio_min_steps},
 };
 
 const Entry *find(const char *name)

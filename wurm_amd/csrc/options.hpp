@@ -26,6 +26,8 @@ struct Options {
     long long policy_wide;           // WURM_POLICY_WIDE           1 = fused actor on policy_wide_kernel even where policy_rollout.hpp's kernels serve (S <= 11, n <= 3)
     long long s9_pair_max_envs;      // WURM_S9_PAIR_MAX_ENVS      9 x 9 rollouts of small batches (rollout_s9_kernel): two waves per env, stepper and helper, up to this many envs (1024; 0 = always one wave per env)
     long long s9_crop_helper_min_steps; // WURM_S9_CROP_HELPER_MIN_STEPS that pair form, partial_n: the helper wave renders the crops in launches of at least this many steps (256; -1 = never)
+    long long s9_trio_max_envs;      // WURM_S9_TRIO_MAX_ENVS      where the helper would render: a second render wave (three waves per env, the trio form) up to this many envs (512)
+    long long s9_trio_min_steps;     // WURM_S9_TRIO_MIN_STEPS     ... in launches of at least this many steps (512; -1 = never)
 };
 
 extern Options opt;

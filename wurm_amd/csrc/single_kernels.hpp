@@ -358,14 +358,21 @@ __global__ __launch_bounds__(256) void rollout_lean_kernel(StepArgs p)
 // the record stores one chunk behind — and wave 0 only steps (DESIGN.md section 4 has the protocol and the measurements).
 // CROPH (with PAIR and partial_n only; single_launch.hpp: launches of at least WURM_S9_CROP_HELPER_MIN_STEPS steps): wave 1
 // also renders the crops, one chunk behind, from what wave 0 records of each step; wave 0's loop holds the transition alone.
-template <int OBSK, bool INJ = false, bool PAIR = false, bool CROPH = false>
+// RW (with CROPH; single_launch.hpp: batches of at most WURM_S9_TRIO_MAX_ENVS envs, launches of at least WURM_S9_TRIO_MIN_STEPS
+// steps): the number of waves that render.  RW = 2 is the trio form, a workgroup of three waves per env: wave 1 renders the
+// first steps of each chunk only, wave 2 renders the others and does nothing else, on wave 1's barrier schedule.
+template <int OBSK, bool INJ = false, bool PAIR = false, bool CROPH = false, int RW = 1>
 __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
 {
     constexpr int CPL = 2, S = 9;
+    // RW = 2: of a chunk's 64 steps the helper renders the first 24 — its other work takes the time of about 9 passes of the
+    // 32 (tools/kernel_timeline.py --render-waves 2) —, of the last chunk's the first half
+    constexpr int S9_TRIO_SHARE = 24, S9_TRIO_LAST_SHARE = 32;
     static_assert(OBSK == WURM_OBS_PARTIAL || OBSK == WURM_OBS_NONE, "9x9 rollout: partial_n or no observation");
     static_assert(!CROPH || (PAIR && OBSK == WURM_OBS_PARTIAL), "9x9 rollout: the helper renders the crops of the pair form");
+    static_assert(RW == 1 || (RW == 2 && CROPH), "9x9 rollout: a second render wave beside a helper that renders");
     const int wave = uniform((int)(threadIdx.x >> 6)), wpb = (int)(blockDim.x >> 6);
-    // PAIR: one workgroup of two waves per env; both take the next line's exit, or neither
+    // PAIR: one workgroup of two (RW = 2: three) waves per env; all take the next line's exit, or none
     const long long env = PAIR ? xcd_block(blockIdx.x, gridDim.x) : xcd_block(blockIdx.x, gridDim.x) * wpb + wave;
     if (env >= p.N) return;
     const Geo g = make_geo<CPL>(S);
@@ -445,11 +452,16 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
     // head code | (food code + 1) << 7 | move entry bits 4-14 << 14 | collisions << 25, and the two halves of the body mask
     // without the head.  Between B(k) and B(k+1) the helper also renders chunk k - 1 from record buffer (k-1) & 1 (last, after
     // the tape load and the record stores); after the last barrier it renders the last chunk.  Same barriers, same parities.
+    // RW = 2: wave 2 passes the helper's barriers — B0, then the verdict, then one per chunk — and between them renders the
+    // steps from S9_TRIO_SHARE / 64 of the chunk on (of the last chunk, which the helper renders with no tape left to load:
+    // from S9_TRIO_LAST_SHARE / 64 on) from the same record buffer, which both renderers only read; the helper renders the
+    // steps before.  No buffer, parity or barrier more.  (The split is even, so that a pass of two steps never straddles it.)
     int *const pair_lds = (int *)(wurm_lds + p.lds_per_wave);
     constexpr int PAIR_CHUNK = 5 * 64, PAIR_REC = 2 * PAIR_CHUNK, PAIR_RECSZ = CROPH ? 4 * 64 : 64, PAIR_LEAN = PAIR_REC + 2 * PAIR_RECSZ;
     const long long n_chunks = (p.T + 63) >> 6;
     if constexpr (PAIR) {
         if (wave != 0) {
+            const bool renders_only = RW == 2 && wave == 2; // wave-uniform: wave 2 of the trio form
             const auto draw_into = [&](const long long k) __attribute__((always_inline)) {
                 const long long t0 = k << 6;
                 const S9Chunk ch = chunk_draw(t0, (int)min((long long)64, p.T - t0));
@@ -476,13 +488,16 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
                 sub = spp == 2 ? lane >> 5 : 0;
                 win = s9_window(spp == 2 ? lane & 31 : lane, p.obs_n);
             }
-            const auto render = [&](const long long k) __attribute__((always_inline)) {
+            const auto render = [&](const long long k, const int share) __attribute__((always_inline)) {
                 const int W2 = (2 * p.obs_n + 1) * (2 * p.obs_n + 1);
                 const long long t0 = k << 6, obs_stride = p.N * p.obs_elems;
                 const int nt = (int)min((long long)64, p.T - t0);
+                // this wave's steps of the chunk: [j0, j1)
+                const int split = RW == 2 ? ((nt * share) >> 6) & ~1 : nt;
+                const int j0 = renders_only ? split : 0, j1 = renders_only ? nt : split;
                 const int *rb = pair_lds + PAIR_REC + (int)(k & 1) * PAIR_RECSZ;
                 const int centre = win.code_d == 0 ? 1 : 0, code_d1 = win.code_d + 1;
-                float *obs_t = p.obs + (t0 * p.N + env) * p.obs_elems;
+                float *obs_t = p.obs + ((t0 + j0) * p.N + env) * p.obs_elems;
                 const auto pass = [&](const int j, const int my_sub) __attribute__((always_inline)) {
                     const int sj = j + my_sub;
                     const int w1 = rb[64 + sj];
@@ -511,34 +526,36 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
                     asm volatile("global_store_dword %0, %1, %6\n\tglobal_store_dword %2, %3, %6\n\tglobal_store_dword %4, %5, %6"
                                  : : "v"(o), "v"(vr), "v"(o + (u32)W2 * 4u), "v"(vg), "v"(o + (u32)W2 * 8u), "v"(vb), "s"(obs_s) : "memory");
                 };
-                int j = 0;
-                for (; j + spp <= nt; j += spp) {
+                int j = j0;
+                for (; j + spp <= j1; j += spp) {
                     pass(j, sub);
                     obs_t += spp * obs_stride;
                 }
-                if (j < nt) pass(j, 0);
+                if (j < j1) pass(j, 0);
             };
-            if (n_chunks > 0) draw_into(0);
+            if (n_chunks > 0 && !renders_only) draw_into(0);
             pair_barrier(); // B0
             if (uniform(pair_lds[PAIR_LEAN]) == 0) return; // the stepper runs rollout_generic, which has no barrier
             for (long long k = 0; k < n_chunks; ++k) {
-                if (k + 1 < n_chunks) draw_into(k + 1); // (reads the tape of chunk k + 1 before chunk k - 1 is written back)
-                if (k > 0) flush_from(k - 1);
+                if (!renders_only) {
+                    if (k + 1 < n_chunks) draw_into(k + 1); // (reads the tape of chunk k + 1 before chunk k - 1 is written back)
+                    if (k > 0) flush_from(k - 1);
+                }
                 if constexpr (CROPH) {
                     WURM_TL_LAP(1);
-                    if (k > 0) render(k - 1);
+                    if (k > 0) render(k - 1, S9_TRIO_SHARE);
                     WURM_TL_LAP(2);
                 }
                 pair_barrier(); // B(k+1)
                 if constexpr (CROPH) WURM_TL_LAP(3);
             }
-            if (n_chunks > 0) flush_from(n_chunks - 1);
+            if (n_chunks > 0 && !renders_only) flush_from(n_chunks - 1);
             if constexpr (CROPH) {
                 WURM_TL_LAP(1);
-                if (n_chunks > 0) render(n_chunks - 1);
+                if (n_chunks > 0) render(n_chunks - 1, S9_TRIO_LAST_SHARE);
                 WURM_TL_LAP(4);
-                // (the helper's laps go over the crop of step 1, the stepper's over that of step 0)
-                if (p.T > 1) WURM_TL_STORE(p.obs + (p.N + env) * p.obs_elems, lane);
+                // (the helper's laps go over the crop of step 1, wave 2's over that of step 2, the stepper's over that of step 0)
+                if (p.T > wave) WURM_TL_STORE(p.obs + (wave * p.N + env) * p.obs_elems, lane);
             }
             return;
         }

@@ -32,7 +32,7 @@ enum Route { R_GENERIC, R_GRID_STEP, R_LANE_STEP, R_GRID_ROLLOUT, R_LANE_ROLLOUT
 // (wurm_single_last_route: the route of the CALLING THREAD's last launch — a diagnostic the tests and bench.py name a launch by; no
 // state that a later call depends on.  Defined in single_snake.hip.)
 extern thread_local Route last_route;
-// (wurm_single_last_waves_per_env: 2 if that launch was rollout_s9_kernel's pair form, else 1)
+// (wurm_single_last_waves_per_env: 2 if that launch was rollout_s9_kernel's pair form, 3 if its trio form, else 1)
 extern thread_local int last_waves_per_env;
 // (wurm_single_last_crop_wave: 1 if that launch was the pair form whose helper wave renders the crops, else 0)
 extern thread_local int last_crop_wave;
@@ -153,6 +153,15 @@ static hipError_t launch_one(Kind kind, const StepArgs &p, dim3 grid, dim3 block
                     p.N * p.obs_elems * 4 < (1ll << 31)) {
                     const size_t clds = (size_t)p.lds_per_wave + (2 * 5 * 64 + 2 * 4 * 64 + 4) * sizeof(int);
                     last_crop_wave = 1;
+                    // The trio form: a second render wave (wave 2) takes most of each chunk's crops off the helper, in small
+                    // batches — the machine has room for a third wave per env there — and launches of several chunks.  Same
+                    // buffers (clds as it is), same barriers, three waves at each: 192 threads per env.
+                    if (p.N <= opt.s9_trio_max_envs && opt.s9_trio_min_steps >= 0 && p.T >= opt.s9_trio_min_steps) {
+                        const dim3 tblock(192);
+                        last_waves_per_env = 3;
+                        if (inj) WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_PARTIAL, true, true, true, 2>), pgrid, tblock, clds, st, p);
+                        else WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_PARTIAL, false, true, true, 2>), pgrid, tblock, clds, st, p);
+                    } else
                     if (inj) WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_PARTIAL, true, true, true>), pgrid, pblock, clds, st, p);
                     else WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_PARTIAL, false, true, true>), pgrid, pblock, clds, st, p);
                 } else

@@ -2,9 +2,13 @@
 reference's experiments/multiagent.py:350-378 is `MultiSnake.act_window` (two launches per step: one `act` for every
 snake of every species, one `step` with the postponed reset), the learners are one `FusedA2CPopulation` with a member per
 species (three launches per window), the log columns of multiagent.py:486-505 are kept on the device by
-`MultiRolloutStats` (two launches per window; copied to the host only when a line is printed).
+`MultiRolloutStats` (two launches per window; copied to the host only when a line is printed).  `--save-video PATH` records
+the first `--video-envs` envs of every `--video-interval`-th window (a .gif or .npy, or an .mp4 where ffmpeg is installed),
+as multiagent.py's `--save-video` does: those windows are replayed for the chosen envs after the fact
+(`MultiSnake.record_start` / `record_frames`, one launch more per recorded window); the others pay nothing.
 
     python examples/a2c_multi_species.py --num-envs 512 --n-agents 4 --n-species 2 --total-steps 200000
+    python examples/a2c_multi_species.py --total-steps 200000 --save-video snakes.gif --video-envs 4 --video-interval 100
     python examples/a2c_multi_species.py --num-envs 8 --n-agents 2 --n-species 2 --size 12 --total-steps 640   # tiny
 
 The policy has the four moves of `FeedforwardAgent`; the env runs with boost=False.
@@ -19,6 +23,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from wurm_amd.agents import FeedforwardAgent  # noqa: E402
 from wurm_amd.envs import MultiSnake  # noqa: E402
+from wurm_amd.recording import WindowRecorder  # noqa: E402
 from wurm_amd.rl import FusedA2CPopulation, MultiRolloutStats  # noqa: E402
 
 
@@ -35,6 +40,9 @@ def main(argv=None):
     ap.add_argument('--entropy', type=float, default=0.01)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--device', default='cuda')
+    ap.add_argument('--save-video', default=None, metavar='PATH', help='record envs of the windows (.gif / .npy / .mp4)')
+    ap.add_argument('--video-envs', type=int, default=4, metavar='K', help='the first K envs are recorded')
+    ap.add_argument('--video-interval', type=int, default=1, help='every this many windows one is recorded')
     args = ap.parse_args(argv)
     N, K, P, T = args.num_envs, args.n_agents, args.n_species, args.update_steps
     if K % P:
@@ -46,10 +54,15 @@ def main(argv=None):
     agents = [FeedforwardAgent(num_actions=4, num_layers=2, hidden_units=64, num_inputs=E).to(env.device) for _ in range(P)]
     learner = FusedA2CPopulation(agents, lr=args.lr, gamma=args.gamma, entropy_coef=args.entropy)
     stats = MultiRolloutStats(env)
+    video = WindowRecorder(env, args.save_video, range(min(args.video_envs, N)), args.video_interval) \
+        if args.save_video else None
     state = env.reset()
     steps, window = 0, 0
     while steps < args.total_steps:
+        rec = video.start(window) if video else None
         out = env.act_window(learner.params, state, T, info=True)
+        if rec is not None:
+            video.finish(rec, out['actions'])
         x0 = torch.stack(list(state.values())).reshape(K * N, E)
         res = learner.update(x0, out)
         stats.update(out)
@@ -68,6 +81,8 @@ def main(argv=None):
                       f'species {s}: reward {r["reward"]:+.4f} done {r["done"]:.4f} size {r["size"]:.3f} life '
                       f'{r["life_length_mean"]:.1f} value loss {vl[s]:.4f} entropy {r["policy_entropy"]:.3f}'
                       for s, r in enumerate(species)), flush=True)
+    if video:
+        video.close()
     return learner
 
 

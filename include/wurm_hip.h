@@ -896,6 +896,38 @@ int wurm_grid_rollout_frames(const float *start, const int64_t *select, const in
                              int64_t num_steps, int start_y, int start_x, uint64_t seed, uint64_t call0,
                              int64_t env_offset, void *stream);
 
+/* ---- frames of a MultiSnake window, after the fact (wurm_amd/csrc/multi_frames.hpp) ------------------------------------
+ * A window of T iterations of step / reset(dones['__all__']) — wurm_multi_rollout, or the per-call launches of
+ * MultiSnake.act_window — is for one env a pure function of its start state, its id env_offset + index, seed, the
+ * configuration block, the window's first call counter call0 (step t uses call0 + 2 t, its reset call0 + 2 t + 1) and the
+ * actions AS GIVEN to the step (it sanitises them itself; the policy's draws come from another counter).  This entry point
+ * re-runs it for num_select chosen envs, one wave each, in one launch, with the loop body of wurm_multi_rollout's kernel, and
+ * writes what `MultiSnake._get_env_images()` shows in front of every step, bit for bit; the window's own kernels are untouched
+ * and pay nothing.
+ *   foods .. boost_this_step   the GATHERED state of the chosen envs before the window, read: foods (num_select, 1, S, S),
+ *                heads / bodies (num_select K, 1, S, S) float, dones / boost_this_step (num_select K) bytes, orientations
+ *                (num_select K) int64, colours (num_select K, 3) int16; env j of them is select[j]'s
+ *   select       (num_select) int64 env indices within the object; random draws use env_offset + select[j], never j
+ *   actions      (num_steps, K, num_envs) int64, the tape of wurm_multi_rollout or `out['actions']` of act_window (column
+ *                k N + i); column select[j] of every snake is read (nullable if num_steps == 0)
+ *   frames       (num_steps + 1, num_select, 3, S, S) int16, written: frame t is the env before step t (after step t - 1
+ *                and its reset); frame num_steps is the state the window leaves behind
+ *   final_*      the state after the last step and its reset, in the layout of the gathered start state, written
+ *   status       (num_select) bytes, written: 0 = replayed; 1 = select[j] is outside [0, num_envs): nothing of that env is
+ *                read, its frames and final state are zeros
+ *   cfg          as wurm_multi_rollout takes it
+ * Refused before any HIP call: a null required pointer, a pointer not aligned to its element, num_select <= 0,
+ * num_envs <= 0, num_steps < 0, num_snakes < 1, size < 3 (WURM_ERR_INVALID_ARG); more than 64 snakes, size > 64 or < 5, an env
+ * whose grids do not fit 160 KB of LDS, more than 2^31 - 1 selected envs (WURM_ERR_UNSUPPORTED): what wurm_multi_rollout
+ * serves is served.  num_steps == 0 writes the one frame and the state back.  One launch on `stream`. */
+int wurm_multi_rollout_frames(const float *foods, const float *heads, const float *bodies, const uint8_t *dones,
+                              const int64_t *orientations, const int16_t *colours, const uint8_t *boost_this_step,
+                              const int64_t *select, const int64_t *actions, int16_t *frames, float *final_foods,
+                              float *final_heads, float *final_bodies, uint8_t *final_dones, int64_t *final_orientations,
+                              int16_t *final_colours, uint8_t *final_boost, uint8_t *status, int64_t num_select,
+                              int64_t num_envs, int num_snakes, int size, int64_t num_steps, const wurm_multi_config *cfg,
+                              uint64_t seed, uint64_t call0, int64_t env_offset, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

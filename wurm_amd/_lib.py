@@ -38,6 +38,7 @@ SYMBOLS = [
     'wurm_single_rollout_frames', 'wurm_grid_rollout_frames',
     'wurm_multi_act',
     'wurm_multi_rollout_stats_workspace_bytes', 'wurm_multi_rollout_stats',
+    'wurm_multi_rollout_frames',
 ]
 
 

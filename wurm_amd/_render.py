@@ -26,7 +26,8 @@ DEFAULT_RENDER_ARGS = {'num_rows': 1, 'num_cols': 1, 'size': 256}   # (single_sn
 
 def tile_frames(frames, render_args: dict = None) -> np.ndarray:
     """The pictures of recorded envs: `frames` is one (k, 3, S, S) frame or a (T, k, 3, S, S) clip of
-    `env.record_frames(...)['frames']` (array or tensor); each frame becomes the (H, W, 3) uint8 picture
+    `env.record_frames(...)['frames']` (array or tensor; uint8 of the single-agent classes or MultiSnake's int16, which is
+    converted as `render('rgb_array')` converts `_get_env_images()`); each frame becomes the (H, W, 3) uint8 picture
     `render('rgb_array')` makes for an env object of num_envs = k with these render_args (None: the reference's default,
     one tile of 256 pixels).  Returns (H, W, 3) for one frame, (T, H, W, 3) for a clip."""
     a = frames.cpu().numpy() if hasattr(frames, 'cpu') else np.asarray(frames)

@@ -883,6 +883,49 @@ class MultiSnake(object):
         from wurm_amd.envs import _multi_act
         return _multi_act.act_window(self, params, state, num_steps, num_species, info)
 
+    # ------------------------------------------------------------------ frames of a fused window (extension;
+    # wurm_amd/envs/_multi_frames.py)
+
+    def record_start(self, select):
+        """Call right before a fused window (`act_window`, `rollout`) whose frames are wanted for the envs `select` (a list
+        or int64 tensor of env indices of this object, any order, repeats allowed; an index outside [0, num_envs) is
+        reported by `record_frames` in `status`, not here; an empty `select` is refused).  Applies a postponed reset,
+        gathers those envs' seven state tensors (foods, heads, bodies, dones, orientations, agent_colours,
+        boost_this_step) and notes the env's call counter, seed, env_offset, size, num_snakes and a copy of the
+        configuration block the window will run with.  Nothing a later call returns changes: no counter is consumed,
+        `policy_calls` is left alone and the tensors are only read.  What it does besides reading: the postponed reset
+        runs now instead of inside the next launch, and a lazy mirror is written out to the tensors (it stays current)."""
+        from wurm_amd.envs import _multi_frames
+        return _multi_frames.record_start(self, select)
+
+    def record_frames(self, rec, actions: torch.Tensor) -> dict:
+        """The frames of the window run right after `rec = env.record_start(select)`: `actions` is `out['actions']` of that
+        `act_window` call, (T, num_snakes * num_envs), or the (T, num_snakes, num_envs) tape given to `rollout` — contiguous
+        int64 on the env's device, the actions as sampled / as given: the replay's step sanitises them as the window's
+        did.  One launch replays the selected envs from their saved state (wurm_amd/csrc/multi_frames.hpp).  Returns
+        `frames` (T + 1, k, 3, S, S) int16 on the device — frame t is what `_get_env_images()[select]` shows before
+        step t, frame T what the window left behind, bit for bit —, `final`, a dict of the seven state tensors of the
+        selected envs after the window (== the env's own at `select`), and `status` (k) uint8: 1 where `select` was
+        outside [0, num_envs) (that env's frames and state are zeros).  `wurm_amd._render.tile_frames` turns the frames
+        into the pictures `render('rgb_array')` makes.
+
+        The rule that ties `rec` to the window: every entry point that draws random numbers for the env takes its
+        counters from `_next_call` — `step` 1, a `reset` 1 (a postponed one when `reset` is CALLED, not when it is
+        applied: `act_window` ends with one, and its counter is spent by then), `_create_envs` 1, a `rollout` of T
+        steps 2 T (step t uses c + 2 t, its reset c + 2 t + 1), an `act_window` of T steps the same 2 T; `act` draws
+        from `policy_calls` and leaves the counter alone.  `record_start` notes the counter c it saw; here the object's
+        counter must be exactly c + 2 T, T = actions.shape[0]: the window, and nothing else that consumed a counter, ran
+        in between — and `record_frames` comes before the next such call.  RuntimeError otherwise, for a `rec` of
+        another object, for actions of another shape, dtype or device, and if the seed, env_offset, size or the
+        configuration block (`food_rate` annealed between the two calls, say) is no longer what `record_start` saw: a
+        window is replayed under ONE configuration.  What cannot be seen here, because it consumes no counter: assigning
+        or editing a state tensor between `record_start` and the window (`final` then differs from the env's own).
+
+        `dtype=torch.half` envs are served: the state the library holds is fp32 whatever `dtype` (as for `rollout`), and
+        the frames are int16 either way."""
+        from wurm_amd.envs import _multi_frames
+        return _multi_frames.record_frames(self, rec, actions)
+
     # ------------------------------------------------------------------ invariants
 
     def check_consistency(self):

@@ -96,9 +96,11 @@ class WindowRecorder(object):
     the fact (`env.record_start` / `env.record_frames`, one launch and one device-to-host copy per recorded window) and its
     frames are tiled row-major into a near-square picture.  A window that is not recorded costs one integer comparison.
     Of two recorded windows in a row the second one's first frame is dropped (it is the first one's last): this assumes
-    that nothing but the windows touches the env between them, as in the examples' loops.
+    that nothing but the windows touches the env between them, as in the examples' loops.  The env is a SingleSnake or a
+    SimpleGridworld (uint8 frames) or a MultiSnake with its `act_window` / `rollout` (examples/a2c_multi_species.py; int16
+    frames, converted as `render('rgb_array')` converts `_get_env_images()`).
 
-        rec = recorder.start(window)                 # in front of env.policy_rollout / env.rollout
+        rec = recorder.start(window)                 # in front of env.policy_rollout / env.act_window / env.rollout
         out = env.policy_rollout(...)
         recorder.finish(rec, out['actions'])         # before the next call on the env; nothing to do if rec is None
         recorder.close()                             # writes the file (VideoRecorder: .mp4 / .npy / GIF)
@@ -130,7 +132,7 @@ class WindowRecorder(object):
         frames = frames.cpu().numpy()
         tiles = self.render_args['num_rows'] * self.render_args['num_cols']
         if tiles > frames.shape[1]:      # (the last row of tiles is not full: black tiles)
-            pad = np.zeros((frames.shape[0], tiles - frames.shape[1]) + frames.shape[2:], np.uint8)
+            pad = np.zeros((frames.shape[0], tiles - frames.shape[1]) + frames.shape[2:], frames.dtype)
             frames = np.concatenate([frames, pad], axis=1)
         self.video.capture_frames(tile_frames(frames, self.render_args))
 

@@ -1,6 +1,8 @@
 """Multi-agent A2C with a feed-forward policy per species, on this project's HIP paths end to end: the acting loop of the
-reference's experiments/multiagent.py:350-378 is `MultiSnake.act_window` (two launches per step: one `act` for every
-snake of every species, one `step` with the postponed reset), the learners are one `FusedA2CPopulation` with a member per
+reference's experiments/multiagent.py:350-378 is `MultiSnake.policy_window` — ONE launch per window where the configuration
+is fused ('partial_n' crops with n <= 3: `--observation partial_3`), else `MultiSnake.act_window`, which `--window act`
+also selects (two launches per step: one `act` for every snake of every species, one `step` with the postponed reset; same
+bits either way, so the two can be run side by side) —, the learners are one `FusedA2CPopulation` with a member per
 species (three launches per window), the log columns of multiagent.py:486-505 are kept on the device by
 `MultiRolloutStats` (two launches per window; copied to the host only when a line is printed).  `--save-video PATH` records
 the first `--video-envs` envs of every `--video-interval`-th window (a .gif or .npy, or an .mp4 where ffmpeg is installed),
@@ -9,6 +11,8 @@ as multiagent.py's `--save-video` does: those windows are replayed for the chose
 
     python examples/a2c_multi_species.py --num-envs 512 --n-agents 4 --n-species 2 --total-steps 200000
     python examples/a2c_multi_species.py --total-steps 200000 --save-video snakes.gif --video-envs 4 --video-interval 100
+    python examples/a2c_multi_species.py --observation partial_3 --total-steps 200000               # the fused window
+    python examples/a2c_multi_species.py --observation partial_3 --window act --total-steps 200000  # the same run, old loop
     python examples/a2c_multi_species.py --num-envs 8 --n-agents 2 --n-species 2 --size 12 --total-steps 640   # tiny
 
 The policy has the four moves of `FeedforwardAgent`; the env runs with boost=False.
@@ -40,6 +44,9 @@ def main(argv=None):
     ap.add_argument('--entropy', type=float, default=0.01)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--device', default='cuda')
+    ap.add_argument('--observation', default='partial_5', help="'partial_n': the crop every agent sees")
+    ap.add_argument('--window', choices=('policy', 'act'), default='policy',
+                    help='policy: MultiSnake.policy_window (one launch per window where fused); act: MultiSnake.act_window')
     ap.add_argument('--save-video', default=None, metavar='PATH', help='record envs of the windows (.gif / .npy / .mp4)')
     ap.add_argument('--video-envs', type=int, default=4, metavar='K', help='the first K envs are recorded')
     ap.add_argument('--video-interval', type=int, default=1, help='every this many windows one is recorded')
@@ -47,20 +54,22 @@ def main(argv=None):
     N, K, P, T = args.num_envs, args.n_agents, args.n_species, args.update_steps
     if K % P:
         raise SystemExit('--n-species must divide --n-agents: a FusedA2CPopulation member owns equally many envs')
-    E = 3 * 11 * 11
+    E = 3 * (2 * int(args.observation.split('_')[1]) + 1) ** 2
     torch.manual_seed(args.seed)
-    env = MultiSnake(num_envs=N, num_snakes=K, size=args.size, observation_mode='partial_5', device=args.device,
+    env = MultiSnake(num_envs=N, num_snakes=K, size=args.size, observation_mode=args.observation, device=args.device,
                      boost=False, food_mode='random_rate', respawn_mode='any', seed=args.seed)
     agents = [FeedforwardAgent(num_actions=4, num_layers=2, hidden_units=64, num_inputs=E).to(env.device) for _ in range(P)]
     learner = FusedA2CPopulation(agents, lr=args.lr, gamma=args.gamma, entropy_coef=args.entropy)
     stats = MultiRolloutStats(env)
     video = WindowRecorder(env, args.save_video, range(min(args.video_envs, N)), args.video_interval) \
         if args.save_video else None
+    run_window = env.policy_window if args.window == 'policy' else env.act_window
+    print(f'window: {args.window}' + (f' (fused: {env.policy_window_fused(P)})' if args.window == 'policy' else ''), flush=True)
     state = env.reset()
     steps, window = 0, 0
     while steps < args.total_steps:
         rec = video.start(window) if video else None
-        out = env.act_window(learner.params, state, T, info=True)
+        out = run_window(learner.params, state, T, info=True)
         if rec is not None:
             video.finish(rec, out['actions'])
         x0 = torch.stack(list(state.values())).reshape(K * N, E)

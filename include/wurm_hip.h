@@ -928,6 +928,51 @@ int wurm_multi_rollout_frames(const float *foods, const float *heads, const floa
                               int64_t num_envs, int num_snakes, int size, int64_t num_steps, const wurm_multi_config *cfg,
                               uint64_t seed, uint64_t call0, int64_t env_offset, void *stream);
 
+/* ---- MultiSnake.policy_window: act, step and reset a whole window in one launch (wurm_amd/csrc/multi_policy_window.hpp) ---
+ * num_steps iterations of  a = wurm_multi_act(params, state); step(a); reset(dones['__all__']); state = observation  for
+ * every env, with the env on chip for the whole window — what MultiSnake.act_window does with two launches per step, bit
+ * for bit.  Step t draws at call0 + 2 t, its reset at call0 + 2 t + 1, the policy at policy_call0 + t from the stream
+ * (env_offset + i) K + k of snake k of env i; snake k acts with row k * num_species / num_snakes of params.  Columns /
+ * rows are agent-major: k * num_envs + i.  A HOST struct of device pointers. */
+typedef struct wurm_multi_policy_window_call {
+    float *foods, *heads, *bodies;    /* in/out: the state, as wurm_multi_rollout takes it; after the call the state behind */
+    uint8_t *dones;                   /*         the last step AND its reset                                                */
+    int64_t *orientations;
+    int16_t *colours;
+    uint8_t *boost_this_step;
+    const uint8_t *pre_done;          /* nullable in (N): wurm_multi_reset(done_env = pre_done, call = pre_call, no
+                                         observation) is applied to every env BEFORE step 0 (wurm_multi_call.pre_done)      */
+    const float *params;              /* (num_species, num_params) fp32, rows in pack_policy_params order                   */
+    const float *obs0;                /* (K, N, E): what the policy acts on at step 0                                       */
+    int64_t *actions;                 /* out (T, K N): as sampled (the step sanitises them itself)                          */
+    float *probs, *values;            /* out (T, K N, 4), (T, K N)                                                          */
+    float *observations;              /* out (T, K N, E): what step t returned, before its reset                            */
+    float *rewards;                   /* out (T, K N)                                                                       */
+    uint8_t *dones_out;               /* out (T, K N)                                                                       */
+    uint8_t *all_done;                /* out (T, N)                                                                         */
+    float *food, *sizes;              /* out (T, K N): info['food_k'], info['size_k']                                       */
+    uint8_t *boost, *snake_collision, *edge_collision; /* out (T, K N)                                                      */
+    int64_t num_envs, num_steps, env_offset, num_params; /* num_params: the row length of params                            */
+    uint64_t seed, call0, pre_call, policy_call0;
+    int num_snakes, size, obs_n, num_species;
+    int waves_per_group;              /* envs per workgroup, 1 .. 4; 0 = chosen by batch size (same results either way)     */
+    wurm_multi_config cfg;
+} wurm_multi_policy_window_call;
+
+/* Which form serves (num_snakes, size, 'partial_<obs_n>', num_species) at num_envs envs: 0 = none (the call would be
+ * refused), 1 = the species' first layers resident in LDS and their heads in registers, 2 = one slot, reloaded whenever
+ * the species changes from one snake to the next (more than 4 species, or first layers that do not fit LDS together).
+ * No HIP call. */
+int wurm_multi_policy_window_plan(int num_snakes, int size, int obs_n, int num_species, int64_t num_envs);
+
+/* Refused before any HIP call: c or a required pointer null (the outputs only when num_steps > 0), a pointer not aligned
+ * to its element, num_envs < 0, num_steps < 0, num_snakes < 1, size < 3, num_species outside [1, num_snakes], num_params
+ * other than the row length for E = 3 (2 obs_n + 1)^2 inputs, waves_per_group outside [0, 4] (WURM_ERR_INVALID_ARG); more
+ * than 64 snakes, size > 64 or < 5, obs_n outside [0, 3], an env whose LDS image does not fit beside one first layer, more
+ * than 2^31 - 1 workgroups (WURM_ERR_UNSUPPORTED).  num_envs == 0 or num_steps == 0: WURM_OK, nothing launched, nothing
+ * read or written (pre_done is NOT applied).  Otherwise ONE launch on `stream`. */
+int wurm_multi_policy_window(const wurm_multi_policy_window_call *c, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

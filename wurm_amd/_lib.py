@@ -39,6 +39,7 @@ SYMBOLS = [
     'wurm_multi_act',
     'wurm_multi_rollout_stats_workspace_bytes', 'wurm_multi_rollout_stats',
     'wurm_multi_rollout_frames',
+    'wurm_multi_policy_window_plan', 'wurm_multi_policy_window',
 ]
 
 
@@ -99,6 +100,19 @@ class MultiSlabs(ctypes.Structure):
     """wurm_multi_slabs of include/wurm_hip.h"""
     _fields_ = [('out_f32', ctypes.c_void_p), ('out_u8', ctypes.c_void_p), ('obs', ctypes.c_void_p),
                 ('obs_after', ctypes.c_void_p), ('steps', ctypes.c_int64), ('obs_elems', ctypes.c_int64)]
+
+
+class MultiPolicyWindowCall(ctypes.Structure):
+    """wurm_multi_policy_window_call of include/wurm_hip.h"""
+    _fields_ = [(n, ctypes.c_void_p) for n in (
+        'foods', 'heads', 'bodies', 'dones', 'orientations', 'colours', 'boost_this_step', 'pre_done', 'params', 'obs0',
+        'actions', 'probs', 'values', 'observations', 'rewards', 'dones_out', 'all_done', 'food', 'sizes', 'boost',
+        'snake_collision', 'edge_collision')] + [
+        ('num_envs', ctypes.c_int64), ('num_steps', ctypes.c_int64), ('env_offset', ctypes.c_int64),
+        ('num_params', ctypes.c_int64), ('seed', ctypes.c_uint64), ('call0', ctypes.c_uint64),
+        ('pre_call', ctypes.c_uint64), ('policy_call0', ctypes.c_uint64), ('num_snakes', ctypes.c_int),
+        ('size', ctypes.c_int), ('obs_n', ctypes.c_int), ('num_species', ctypes.c_int),
+        ('waves_per_group', ctypes.c_int), ('cfg', MultiConfig)]
 
 
 def multi_config(num_snakes, boost, food_on_death_prob, boost_cost_prob, food_mode, food_rate, reward_on_death,

@@ -11,7 +11,9 @@ from the Philox stream of `env_id_of(i, k, K, env_offset)` = (env_offset + i) * 
 step stays postponed across an `act` and the env's trajectory for given actions does not depend on who chose them.
 
 What is not here: the 8-action boost head (the shared policy spec and `FeedforwardAgent` have 4 actions: with `boost=True`
-the policy never boosts), the reference's ConvAgent / GRUAgent, and fusion into the env kernel.
+the policy never boosts) and the reference's ConvAgent / GRUAgent.  The window fused into ONE launch with the env kernel is
+`MultiSnake.policy_window` (wurm_amd/envs/_multi_policy_window.py), which returns what `act_window` returns, bit for bit;
+`act_window` is its yardstick and what it runs for the configurations it does not fuse.
 """
 import torch
 

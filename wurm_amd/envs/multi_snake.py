@@ -883,6 +883,30 @@ class MultiSnake(object):
         from wurm_amd.envs import _multi_act
         return _multi_act.act_window(self, params, state, num_steps, num_species, info)
 
+    # (tests / side-by-side runs) True: `policy_window` runs `act_window` whatever the configuration; envs per workgroup of
+    # the fused launch, 0 = chosen by batch size — neither changes a result
+    _force_act_window = False
+    _policy_window_wpb = 0
+
+    def policy_window(self, params: torch.Tensor, state, num_steps: int, num_species: int = None,
+                      info: bool = False) -> dict:
+        """`act_window` in ONE launch: the same arguments, the same dict (keys, shapes, dtypes, bits), the same counters
+        afterwards (`policy_calls` + T, the env's own + 2 T), and `FusedA2CPopulation.update`, `MultiRolloutStats.update`
+        and `record_start` / `record_frames` take the result as they take `act_window`'s.  The envs stay on chip for the T
+        steps; per step the kernel draws the K actions from the crops it holds, steps, observes and resets
+        (wurm_amd/csrc/multi_policy_window.hpp).  A reset(done) postponed in front of the window goes into the launch;
+        the last step's reset is applied inside it rather than left postponed — nothing a later call returns differs.
+        Fused: 'partial_n' with n <= 3, dtype=torch.float, any num_snakes and num_species (`policy_window_fused`);
+        everything else `act_window` serves runs `act_window`."""
+        from wurm_amd.envs import _multi_policy_window
+        return _multi_policy_window.policy_window(self, params, state, num_steps, num_species, info)
+
+    def policy_window_fused(self, num_species: int = 1) -> bool:
+        """Does `policy_window` run the fused launch for this env as it is configured now and `num_species` species (else
+        it runs `act_window`)?  No device work."""
+        from wurm_amd.envs import _multi_policy_window
+        return _multi_policy_window.plan(self, num_species) != 0
+
     # ------------------------------------------------------------------ frames of a fused window (extension;
     # wurm_amd/envs/_multi_frames.py)
 

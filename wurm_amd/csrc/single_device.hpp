@@ -1159,6 +1159,53 @@ __device__ __forceinline__ void set_lane(S9CropRec &r, int ent, int c, int food,
         : "m0");
 #pragma clang diagnostic pop
 }
+// The trio form's record of a plain move: the move entry and the body mask only (r.c stays unused, r.food is written by eating
+// steps alone); the render waves rebuild the head and food codes of a whole chunk from those (s9_rebuild_crop_words).
+__device__ __forceinline__ void set_lane(S9CropRec &r, int ent, u64 body, int dst)
+{
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm" // (m0: as above)
+    asm("s_mov_b32 m0, %6\n\t"
+        "v_writelane_b32 %0, %3, m0\n\t"
+        "v_writelane_b32 %1, %4, m0\n\t"
+        "v_writelane_b32 %2, %5, m0"
+        : "+v"(r.ent), "+v"(r.body_lo), "+v"(r.body_hi)
+        : "s"(ent), "s"((int)(u32)body), "s"((int)(u32)(body >> 32)), "s"(dst)
+        : "m0");
+#pragma clang diagnostic pop
+}
+
+// The crop words of a chunk's 64 steps, step j in lane j, from what the stepper of the trio form hands over (rollout_s9_kernel):
+//   rec   action & 7 | ate << 3 | collisions << 4 of step j
+//   pw    the crop word of step j without its head code, and with a food field (bits 7-13: food code + 1) that only an eating
+//         step defines: the cell drawn on that step
+//   ra/rb the would-be reset of step j (S9Reset)
+//   c0/f0 head code and food code the stepper entered the chunk with
+// Head code of step j: c0, or the head code of the last reset before j, plus the code steps since — integer sums, so the same
+// integer as the stepper's chain of s_add_i32 whatever the order (the caller masks it like the stepper did).  Shown food of
+// step j: what the last of these left: an eating step at or before j, a reset before j, the chunk start.  An eating step does
+// not collide (no food on the ring or under the body), so "the last" is decided by the step indices alone.
+__device__ __forceinline__ int s9_rebuild_crop_words(int rec, int pw, int ra, int rb, int c0, int f0, int lane)
+{
+    int P = (pw << 10) >> 26; // the code step of the move entry, then its inclusive prefix sum over the lanes
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) {
+        const int below = __shfl_up(P, s, 64);
+        P += lane >= s ? below : 0;
+    }
+    const u64 resets = lane_mask((rec >> 4) != 0), eats = lane_mask(((rec >> 3) & 1) != 0);
+    const u64 before = (1ull << lane) - 1ull, upto = before | (1ull << lane);
+    const u64 rbef = resets & before, eupto = eats & upto;
+    const int r = rbef ? 63 - __clzll((long long)rbef) : -1;   // the last reset before this step
+    const int e = eupto ? 63 - __clzll((long long)eupto) : -1; // the last eating step up to this one
+    // from lane r: head code of the new snake less the steps up to there, and its food; from lane e: the food drawn there
+    const int base_r = __shfl((rb & 127) - P, r & 63, 64);
+    const int food_r = __shfl(((ra >> 2) + 1) & 127, r & 63, 64);
+    const int food_e = __shfl((pw >> 7) & 127, e & 63, 64);
+    const int c = (r >= 0 ? base_r : c0) + P;
+    const int food1 = e > r ? food_e : r >= 0 ? food_r : (f0 + 1) & 127;
+    return (c & 127) | (food1 << 7) | (pw & ~0x3FFF);
+}
 
 // The partial_n window cell a lane of the 9 x 9 rollout renders, for window-cell index wl (lanes past the window repeat
 // its last cell: same address, same value): its offset from the head in rows, columns and codes, what an occupied cell

@@ -371,6 +371,7 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
     static_assert(OBSK == WURM_OBS_PARTIAL || OBSK == WURM_OBS_NONE, "9x9 rollout: partial_n or no observation");
     static_assert(!CROPH || (PAIR && OBSK == WURM_OBS_PARTIAL), "9x9 rollout: the helper renders the crops of the pair form");
     static_assert(RW == 1 || (RW == 2 && CROPH), "9x9 rollout: a second render wave beside a helper that renders");
+    constexpr bool REBUILD = CROPH && RW == 2; // the trio form: the render waves rebuild the head and food codes of a chunk
     const int wave = uniform((int)(threadIdx.x >> 6)), wpb = (int)(blockDim.x >> 6);
     // PAIR: one workgroup of two (RW = 2: three) waves per env; all take the next line's exit, or none
     const long long env = PAIR ? xcd_block(blockIdx.x, gridDim.x) : xcd_block(blockIdx.x, gridDim.x) * wpb + wave;
@@ -455,9 +456,18 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
     // RW = 2: wave 2 passes the helper's barriers — B0, then the verdict, then one per chunk — and between them renders the
     // steps from S9_TRIO_SHARE / 64 of the chunk on (of the last chunk, which the helper renders with no tape left to load:
     // from S9_TRIO_LAST_SHARE / 64 on) from the same record buffer, which both renderers only read; the helper renders the
-    // steps before.  No buffer, parity or barrier more.  (The split is even, so that a pass of two steps never straddles it.)
+    // steps before.  No parity or barrier more.  (The split is even, so that a pass of two steps never straddles it.)
+    // REBUILD (RW = 2): the stepper records per step only the move entry and the body mask, and on an eating step the food it
+    // drew; plane 1 of a record buffer holds the crop word without the head code, its food field defined on eating steps
+    // alone.  The record buffer grows to six planes and two dwords: at the START of chunk k the stepper copies the chunk's
+    // would-be reset words (planes 4, 5) and the head and food code it enters the chunk with (dwords 384, 385) into record
+    // buffer k & 1, whose last readers passed B(k); so they live as long as the record — the chunk buffer they come from is
+    // overwritten by the helper (chunk k + 2) just while chunk k is rendered.  Each render wave rebuilds the crop words of
+    // all 64 steps (s9_rebuild_crop_words, step j in lane j) into a plane of its own behind the verdict, which no other wave
+    // touches, and renders its share from there: both rebuild, neither waits for the other.
     int *const pair_lds = (int *)(wurm_lds + p.lds_per_wave);
-    constexpr int PAIR_CHUNK = 5 * 64, PAIR_REC = 2 * PAIR_CHUNK, PAIR_RECSZ = CROPH ? 4 * 64 : 64, PAIR_LEAN = PAIR_REC + 2 * PAIR_RECSZ;
+    constexpr int PAIR_CHUNK = 5 * 64, PAIR_REC = 2 * PAIR_CHUNK, PAIR_RECSZ = REBUILD ? 6 * 64 + 4 : CROPH ? 4 * 64 : 64;
+    constexpr int PAIR_LEAN = PAIR_REC + 2 * PAIR_RECSZ, PAIR_OWN = PAIR_LEAN + 4;
     const long long n_chunks = (p.T + 63) >> 6;
     if constexpr (PAIR) {
         if (wave != 0) {
@@ -496,11 +506,17 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
                 const int split = RW == 2 ? ((nt * share) >> 6) & ~1 : nt;
                 const int j0 = renders_only ? split : 0, j1 = renders_only ? nt : split;
                 const int *rb = pair_lds + PAIR_REC + (int)(k & 1) * PAIR_RECSZ;
+                const int *words = rb + 64; // the crop word of step j at words[j]
+                if constexpr (REBUILD) {
+                    int *own = pair_lds + PAIR_OWN + (wave - 1) * 64;
+                    own[lane] = s9_rebuild_crop_words(rb[lane], rb[64 + lane], rb[256 + lane], rb[320 + lane], uniform(rb[384]), uniform(rb[385]), lane);
+                    words = own;
+                }
                 const int centre = win.code_d == 0 ? 1 : 0, code_d1 = win.code_d + 1;
                 float *obs_t = p.obs + ((t0 + j0) * p.N + env) * p.obs_elems;
                 const auto pass = [&](const int j, const int my_sub) __attribute__((always_inline)) {
                     const int sj = j + my_sub;
-                    const int w1 = rb[64 + sj];
+                    const int w1 = words[sj];
                     const u64 body = (u64)(u32)rb[128 + sj] | ((u64)(u32)rb[192 + sj] << 32);
                     const int c = w1 & 127;
                     // (both shifts read the low 6 bits of their amount, which are those of the head code in w1)
@@ -643,6 +659,12 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
         // what lane j keeps of step t0 + j: its move entry, whether it ate, self collision | edge collision << 1
         int my_rec = 0, my_ate = 0, my_fl = 0;
         S9CropRec crop_rec = {0, 0, 0, 0, 0};        // CROPH: what the helper renders step t0 + j's crop from, in lane j
+        if constexpr (REBUILD) { // what the render waves rebuild the chunk's head and food codes from (protocol: above)
+            int *rb = pair_lds + PAIR_REC + (int)((t0 >> 6) & 1) * PAIR_RECSZ;
+            rb[256 + lane] = my_reset.a;
+            rb[320 + lane] = my_reset.b;
+            if (lane == 0) { rb[384] = c; rb[385] = foodc; }
+        }
         {   // re-base the clocks so that they cannot overflow however long the tape is
             const int T = T1 - 1;
             ex = max(ex - T, 0);
@@ -671,7 +693,9 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
             // is the length growing by one
             asm("s_cmp_lg_u32 %1, %2\n\ts_addc_u32 %0, %0, 0" : "+s"(T1) : "s"(c), "s"(foodc) : "scc");
             // CROPH: the record of a plain move, of a collision and of the reset behind it; a step that eats rewrites its lane below
-            if constexpr (CROPH) set_lane(crop_rec, ent, c, foodc, body_moved, j);
+            // (REBUILD: without the head and food codes)
+            if constexpr (REBUILD) set_lane(crop_rec, ent, body_moved, j);
+            else if constexpr (CROPH) set_lane(crop_rec, ent, c, foodc, body_moved, j);
             u64 body = body_moved;
             const u64 head = 1ull << (c & 63);
             ex = keep_in_lane(ex, G, head);          // :258-262 (a head on the ring may land in a wrong lane: it is reset below)
@@ -793,6 +817,7 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
                 // code or a negative head code could not spill into a neighbour
                 int *rb = pair_lds + PAIR_REC + (int)((t0 >> 6) & 1) * PAIR_RECSZ + lane;
                 my_rec = crop_rec.ent;
+                // (REBUILD: crop_rec.c stays 0, the food field holds what an eating step drew; the render waves fill both in)
                 rb[64] = (crop_rec.c & 127) | (((crop_rec.food + 1) & 127) << 7) | (((my_rec >> 4) & 0x7FF) << 14) | ((my_fl & 3) << 25);
                 rb[128] = crop_rec.body_lo;
                 rb[192] = crop_rec.body_hi;

@@ -47,7 +47,8 @@ def s9_timeline():
     observation stores; pair: the barrier and the LDS reads), 2 prologue arithmetic (one wave only), 3 step loop, 4 flush
     (one wave: the record stores issued; pair: the record's LDS write and the barrier, that is the stepper's wait for the helper).
     Slots of the helper with --crop-helper 1: 1 tape load, draw and record stores (and, first, B0), 2 rendering of the chunk
-    before, 3 wait at the chunk barrier, 4 rendering of the last chunk, after the stepper has finished"""
+    before, 3 wait at the chunk barrier, 4 rendering of the last chunk, after the stepper has finished; the trio form's render
+    waves also 5: rebuilding the crop words and body masks of a chunk (all chunks; slots 2 and 4 are the passes alone then)"""
     import numpy as np
     import torch
     from wurm_amd import _lib
@@ -102,7 +103,7 @@ def s9_timeline():
     hs, hl = hs[(hl > 0) & (hl < 10 ** 9)], hl[(hl > 0) & (hl < 10 ** 9)]
     print(f'helper wave: {len(hl)} samples')
     for k, name in [(1, 'tape, draw, records (+ B0)'), (2, 'rendering, chunks 0 .. C-2'), (3, 'wait at the chunk barrier'),
-                    (4, 'rendering, last chunk')]:
+                    (4, 'rendering, last chunk'), (5, 'rebuild, all chunks')]:
         c = hs[:, k]
         print(f'  {name:>26s} p10 {int(np.percentile(c, 10)):7d}  p50 {int(np.median(c)):7d}  p90 {int(np.percentile(c, 90)):7d}  '
               f'max {int(c.max()):7d}   {100.0 * np.median(c) / np.median(hl):5.1f} % of p50 life')
@@ -120,7 +121,7 @@ def s9_timeline():
     ws, wl = ws[(wl > 0) & (wl < 10 ** 9)], wl[(wl > 0) & (wl < 10 ** 9)]
     print(f'wave 2 (renders only): {len(wl)} samples')
     for k, name in [(1, 'B0 and loop overhead'), (2, 'rendering, chunks 0 .. C-2'), (3, 'wait at the chunk barrier'),
-                    (4, 'rendering, last chunk')]:
+                    (4, 'rendering, last chunk'), (5, 'rebuild, all chunks')]:
         c = ws[:, k]
         print(f'  {name:>26s} p10 {int(np.percentile(c, 10)):7d}  p50 {int(np.median(c)):7d}  p90 {int(np.percentile(c, 90)):7d}  '
               f'max {int(c.max()):7d}   {100.0 * np.median(c) / np.median(wl):5.1f} % of p50 life')
@@ -128,6 +129,8 @@ def s9_timeline():
     print(f'per chunk, p50: wave 2 renders {int(np.median(ws[:, 2])) // max(C - 1, 1)} ticks and waits at the barrier '
           f'{int(np.median(ws[:, 3])) // C}; the helper renders and works {(int(np.median(hs[:, 2])) + int(np.median(hs[:, 1]))) // C} '
           f'and waits {int(np.median(hs[:, 3])) // C}; the stepper steps {int(np.median(st[:, 3])) // C}')
+    print(f'per chunk, p50: the helper rebuilds in {int(np.median(hs[:, 5])) // C} ticks, wave 2 in {int(np.median(ws[:, 5])) // C} '
+          f'(0: a library whose render waves leave no such lap)')
 
 
 if args.kernel == 's9':

@@ -1159,21 +1159,9 @@ __device__ __forceinline__ void set_lane(S9CropRec &r, int ent, int c, int food,
         : "m0");
 #pragma clang diagnostic pop
 }
-// The trio form's record of a plain move: the move entry and the body mask only (r.c stays unused, r.food is written by eating
-// steps alone); the render waves rebuild the head and food codes of a whole chunk from those (s9_rebuild_crop_words).
-__device__ __forceinline__ void set_lane(S9CropRec &r, int ent, u64 body, int dst)
-{
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Winline-asm" // (m0: as above)
-    asm("s_mov_b32 m0, %6\n\t"
-        "v_writelane_b32 %0, %3, m0\n\t"
-        "v_writelane_b32 %1, %4, m0\n\t"
-        "v_writelane_b32 %2, %5, m0"
-        : "+v"(r.ent), "+v"(r.body_lo), "+v"(r.body_hi)
-        : "s"(ent), "s"((int)(u32)body), "s"((int)(u32)(body >> 32)), "s"(dst)
-        : "m0");
-#pragma clang diagnostic pop
-}
+// (The trio form's record of a plain move is the move entry alone, one set_lane into r.ent: r.c and the body halves stay unused,
+// r.food is written by eating steps alone; the render waves rebuild the head codes, the food codes and the body masks of a whole
+// chunk from that: s9_rebuild_crop_words, s9_rebuild_body.)
 
 // The crop words of a chunk's 64 steps, step j in lane j, from what the stepper of the trio form hands over (rollout_s9_kernel):
 //   rec   action & 7 | ate << 3 | collisions << 4 of step j
@@ -1205,6 +1193,57 @@ __device__ __forceinline__ int s9_rebuild_crop_words(int rec, int pw, int ra, in
     const int c = (r >= 0 ? base_r : c0) + P;
     const int food1 = e > r ? food_e : r >= 0 ? food_r : (f0 + 1) & 127;
     return (c & 127) | (food1 << 7) | (pw & ~0x3FFF);
+}
+
+// The body mask without the head of a chunk's 64 steps, step j in lane j (bit x: the cell of code x), from what the stepper of
+// the trio form hands over (rollout_s9_kernel) — the integer its compare `ex > T` gave on step j:
+//   rec    action & 7 | ate << 3 | collisions << 4 of step j
+//   word   the rebuilt crop word of step j (s9_rebuild_crop_words): bits 0-6 the head code after the move
+//   rb     the would-be reset of step j (S9Reset::b: head | seed << 7 | tail << 14 of the new snake)
+//   ex0    the clock of the cell whose code is `lane`, on entering the chunk, re-based to the clock 0 (0: free)
+//   len0   the length on entering the chunk
+// With r the last reset before step j (none: the chunk start) and len_j the length after step j's move — 3, or len0 in the
+// chunk's first segment, plus the eating steps behind r up to j, for the clock stands still on a step that eats —, a cell is
+// body on step j if the head stood there on a step i with 0 < j - i < len_j: the head wrote the clock G_i there, G_j - G_i =
+// j - i and len_j = G_j - T_j, so that is G_i > T_j.  The head of step i is
+//   * the head code of step i's crop word for r < i (no reset in between: the head is inside the ring, one lane, one bit);
+//   * the head, seed and tail cell of reset r's new snake for i = r, r - 1, r - 2: the reset gave them the clocks the head
+//     would have written there (T + 3, T + 2, T + 1), and nothing else survived it.  The window never reaches behind r - 2:
+//     len_j - 3 eating steps lie between r and j;
+//   * before the chunk's first reset, for i < 0, whatever the chunk-start clocks say: the cell of code x is body while
+//     ex0[x] > T_j, and T_j is the number of steps up to j that did not eat.  No assumption on the clocks being consecutive.
+// A cell the head visited twice is body if either visit says so (the later clock is the larger one).  A code that is no
+// lane's (a hand-made reset word) sets no bit, as in the stepper, which compares lanes with codes.
+__device__ __forceinline__ u64 s9_rebuild_body(int rec, int word, int rb, int ex0, int len0, int lane)
+{
+    const u64 resets = lane_mask((rec >> 4) != 0), eats = lane_mask(((rec >> 3) & 1) != 0);
+    const u64 before = (1ull << lane) - 1ull, upto = before | (1ull << lane);
+    const u64 rbef = resets & before;
+    const int r = rbef ? 63 - __clzll((long long)rbef) : -1;             // the last reset before this step (r <= 62)
+    const u64 behind_r = r >= 0 ? ~((2ull << r) - 1ull) : ~0ull;
+    const int grown = popc64(eats & upto & behind_r);                    // eating steps behind r up to this step
+    const int len = (r >= 0 ? 3 : len0) + grown;
+    const int nb = __shfl(rb, r & 63, 64);
+    const int new_head = nb & 127, new_seed = (nb >> 7) & 127, new_tail = nb >> 14;
+    u64 body = 0;
+    // the chunk-start clocks: one ballot over the cells per clock value, taken by the steps at which the clock has that value
+    const int clock = r >= 0 ? -1 : lane + 1 - grown;
+    for (int t = 0; t <= 64; ++t) {
+        const u64 later = lane_mask(ex0 > t);
+        if (later == 0) break;
+        body = clock == t ? later : body;
+    }
+    // the trail: the head of d steps ago, for every d below the longest length among the 64 steps
+    const int hc = word & 63;
+    const int longest = min(wave_max_i32(len), 64);
+    for (int d = 1; d < longest; ++d) {
+        const int i = lane - d;
+        const int moved = __shfl_up(hc, (unsigned)d, 64);                // (lanes below d get their own: i < 0, not used)
+        const int code = i > r ? moved : i == r ? new_head : i == r - 1 ? new_seed : new_tail;
+        const bool in_window = d < len && (i > r || r >= 0) && (unsigned)code < 64u;
+        body |= in_window ? 1ull << (code & 63) : 0ull;
+    }
+    return body;
 }
 
 // The partial_n window cell a lane of the 9 x 9 rollout renders, for window-cell index wl (lanes past the window repeat

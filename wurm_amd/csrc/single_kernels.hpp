@@ -457,16 +457,18 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
     // steps from S9_TRIO_SHARE / 64 of the chunk on (of the last chunk, which the helper renders with no tape left to load:
     // from S9_TRIO_LAST_SHARE / 64 on) from the same record buffer, which both renderers only read; the helper renders the
     // steps before.  No parity or barrier more.  (The split is even, so that a pass of two steps never straddles it.)
-    // REBUILD (RW = 2): the stepper records per step only the move entry and the body mask, and on an eating step the food it
-    // drew; plane 1 of a record buffer holds the crop word without the head code, its food field defined on eating steps
-    // alone.  The record buffer grows to six planes and two dwords: at the START of chunk k the stepper copies the chunk's
-    // would-be reset words (planes 4, 5) and the head and food code it enters the chunk with (dwords 384, 385) into record
-    // buffer k & 1, whose last readers passed B(k); so they live as long as the record — the chunk buffer they come from is
-    // overwritten by the helper (chunk k + 2) just while chunk k is rendered.  Each render wave rebuilds the crop words of
-    // all 64 steps (s9_rebuild_crop_words, step j in lane j) into a plane of its own behind the verdict, which no other wave
-    // touches, and renders its share from there: both rebuild, neither waits for the other.
+    // REBUILD (RW = 2): the stepper records per step only the move entry, and on an eating step the food it drew; plane 1 of
+    // a record buffer holds the crop word without the head code, its food field defined on eating steps alone, and there
+    // are no body planes.  The record buffer is five planes and three dwords: at the START of chunk k the stepper copies the
+    // re-based clocks `ex` it enters the chunk with (plane 2, one clock per cell), the chunk's would-be reset words (planes
+    // 3, 4) and the head code, food code and length it enters the chunk with (dwords 320-322) into record buffer k & 1,
+    // whose last readers passed B(k); so they live as long as the record — the chunk buffer the reset words come from is
+    // overwritten by the helper (chunk k + 2) just while chunk k is rendered.  Each render wave rebuilds the crop words
+    // (s9_rebuild_crop_words) and the body masks (s9_rebuild_body) of all 64 steps, step j in lane j, into three planes of
+    // its own behind the verdict, which no other wave touches, and renders its share from there: both rebuild, neither
+    // waits for the other.
     int *const pair_lds = (int *)(wurm_lds + p.lds_per_wave);
-    constexpr int PAIR_CHUNK = 5 * 64, PAIR_REC = 2 * PAIR_CHUNK, PAIR_RECSZ = REBUILD ? 6 * 64 + 4 : CROPH ? 4 * 64 : 64;
+    constexpr int PAIR_CHUNK = 5 * 64, PAIR_REC = 2 * PAIR_CHUNK, PAIR_RECSZ = REBUILD ? 5 * 64 + 4 : CROPH ? 4 * 64 : 64;
     constexpr int PAIR_LEAN = PAIR_REC + 2 * PAIR_RECSZ, PAIR_OWN = PAIR_LEAN + 4;
     const long long n_chunks = (p.T + 63) >> 6;
     if constexpr (PAIR) {
@@ -506,18 +508,25 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
                 const int split = RW == 2 ? ((nt * share) >> 6) & ~1 : nt;
                 const int j0 = renders_only ? split : 0, j1 = renders_only ? nt : split;
                 const int *rb = pair_lds + PAIR_REC + (int)(k & 1) * PAIR_RECSZ;
-                const int *words = rb + 64; // the crop word of step j at words[j]
+                // the crop word of step j at words[j], the halves of its body mask without the head at body_lo[j], body_hi[j]
+                const int *words = rb + 64, *body_lo = rb + 128, *body_hi = rb + 192;
                 if constexpr (REBUILD) {
-                    int *own = pair_lds + PAIR_OWN + (wave - 1) * 64;
-                    own[lane] = s9_rebuild_crop_words(rb[lane], rb[64 + lane], rb[256 + lane], rb[320 + lane], uniform(rb[384]), uniform(rb[385]), lane);
-                    words = own;
+                    int *own = pair_lds + PAIR_OWN + (wave - 1) * 3 * 64;
+                    const int rec = rb[lane], reset_b = rb[256 + lane];
+                    const int w1 = s9_rebuild_crop_words(rec, rb[64 + lane], rb[192 + lane], reset_b, uniform(rb[320]), uniform(rb[321]), lane);
+                    const u64 body = s9_rebuild_body(rec, w1, reset_b, rb[128 + lane], uniform(rb[322]), lane);
+                    own[lane] = w1;
+                    own[64 + lane] = (int)(u32)body;
+                    own[128 + lane] = (int)(u32)(body >> 32);
+                    words = own; body_lo = own + 64; body_hi = own + 128;
+                    WURM_TL_LAP(5); // (the render waves' slot 5: both rebuilds, LDS reads and writes included)
                 }
                 const int centre = win.code_d == 0 ? 1 : 0, code_d1 = win.code_d + 1;
                 float *obs_t = p.obs + ((t0 + j0) * p.N + env) * p.obs_elems;
                 const auto pass = [&](const int j, const int my_sub) __attribute__((always_inline)) {
                     const int sj = j + my_sub;
                     const int w1 = words[sj];
-                    const u64 body = (u64)(u32)rb[128 + sj] | ((u64)(u32)rb[192 + sj] << 32);
+                    const u64 body = (u64)(u32)body_lo[sj] | ((u64)(u32)body_hi[sj] << 32);
                     const int c = w1 & 127;
                     // (both shifts read the low 6 bits of their amount, which are those of the head code in w1)
                     unsigned inside = (u32)(win.live_tab >> (w1 & 63)) & 1u;
@@ -659,17 +668,18 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
         // what lane j keeps of step t0 + j: its move entry, whether it ate, self collision | edge collision << 1
         int my_rec = 0, my_ate = 0, my_fl = 0;
         S9CropRec crop_rec = {0, 0, 0, 0, 0};        // CROPH: what the helper renders step t0 + j's crop from, in lane j
-        if constexpr (REBUILD) { // what the render waves rebuild the chunk's head and food codes from (protocol: above)
-            int *rb = pair_lds + PAIR_REC + (int)((t0 >> 6) & 1) * PAIR_RECSZ;
-            rb[256 + lane] = my_reset.a;
-            rb[320 + lane] = my_reset.b;
-            if (lane == 0) { rb[384] = c; rb[385] = foodc; }
-        }
         {   // re-base the clocks so that they cannot overflow however long the tape is
             const int T = T1 - 1;
             ex = max(ex - T, 0);
             G -= T;
             T1 = 1;
+        }
+        if constexpr (REBUILD) { // what the render waves rebuild the chunk's head codes, food codes and body masks from (protocol: above)
+            int *rb = pair_lds + PAIR_REC + (int)((t0 >> 6) & 1) * PAIR_RECSZ;
+            rb[128 + lane] = ex;
+            rb[192 + lane] = my_reset.a;
+            rb[256 + lane] = my_reset.b;
+            if (lane == 0) { rb[320] = c; rb[321] = foodc; rb[322] = G; } // (the clock is 0 here: G is the length)
         }
 
         // one step: step t0 + j of this env.  Inlined U + 1 times below (U copies in the unrolled body, one in the tail
@@ -693,8 +703,8 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
             // is the length growing by one
             asm("s_cmp_lg_u32 %1, %2\n\ts_addc_u32 %0, %0, 0" : "+s"(T1) : "s"(c), "s"(foodc) : "scc");
             // CROPH: the record of a plain move, of a collision and of the reset behind it; a step that eats rewrites its lane below
-            // (REBUILD: without the head and food codes)
-            if constexpr (REBUILD) set_lane(crop_rec, ent, body_moved, j);
+            // (REBUILD: the move entry alone)
+            if constexpr (REBUILD) crop_rec.ent = set_lane(crop_rec.ent, ent, j);
             else if constexpr (CROPH) set_lane(crop_rec, ent, c, foodc, body_moved, j);
             u64 body = body_moved;
             const u64 head = 1ull << (c & 63);
@@ -738,8 +748,9 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
                         }
                     }
                     XF = RING | (foodc >= 0 ? 1ull << foodc : 0);
-                    if constexpr (CROPH) { // the crop shows the food drawn just now and the body that kept its tail
+                    if constexpr (CROPH) // the crop shows the food drawn just now and the body that kept its tail
                         crop_rec.food = set_lane(crop_rec.food, foodc, j);
+                    if constexpr (CROPH && !REBUILD) { // (REBUILD: the render waves know that the clock stood still)
                         crop_rec.body_lo = set_lane(crop_rec.body_lo, (int)(u32)body, j);
                         crop_rec.body_hi = set_lane(crop_rec.body_hi, (int)(u32)(body >> 32), j);
                     }
@@ -819,8 +830,10 @@ __global__ __launch_bounds__(256) void rollout_s9_kernel(StepArgs p)
                 my_rec = crop_rec.ent;
                 // (REBUILD: crop_rec.c stays 0, the food field holds what an eating step drew; the render waves fill both in)
                 rb[64] = (crop_rec.c & 127) | (((crop_rec.food + 1) & 127) << 7) | (((my_rec >> 4) & 0x7FF) << 14) | ((my_fl & 3) << 25);
-                rb[128] = crop_rec.body_lo;
-                rb[192] = crop_rec.body_hi;
+                if constexpr (!REBUILD) {
+                    rb[128] = crop_rec.body_lo;
+                    rb[192] = crop_rec.body_hi;
+                }
                 rb[0] = ((my_rec >> 12) & 7) | (my_ate << 3) | (my_fl << 4);
             } else {
                 pair_lds[PAIR_REC + (int)((t0 >> 6) & 1) * 64 + lane] = ((my_rec >> 12) & 7) | (my_ate << 3) | (my_fl << 4);

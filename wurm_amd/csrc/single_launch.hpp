@@ -155,12 +155,13 @@ static hipError_t launch_one(Kind kind, const StepArgs &p, dim3 grid, dim3 block
                     last_crop_wave = 1;
                     // The trio form: a second render wave (wave 2) takes most of each chunk's crops off the helper, in small
                     // batches — the machine has room for a third wave per env there — and launches of several chunks.  Same
-                    // barriers, three waves at each: 192 threads per env.  Its render waves rebuild the head and food codes
-                    // the stepper no longer records: record buffers of 6 x 64 + 4 dwords (two planes of reset words, the
-                    // chunk-start codes) and a plane of rebuilt crop words for each render wave, behind the verdict.
+                    // barriers, three waves at each: 192 threads per env.  Its render waves rebuild the head codes, food codes
+                    // and body masks the stepper no longer records: record buffers of 5 x 64 + 4 dwords (the chunk-start
+                    // clocks, two planes of reset words, the chunk-start codes and length) and three planes for each render
+                    // wave (rebuilt crop words, the two halves of the rebuilt body masks), behind the verdict.
                     if (p.N <= opt.s9_trio_max_envs && opt.s9_trio_min_steps >= 0 && p.T >= opt.s9_trio_min_steps) {
                         const dim3 tblock(192);
-                        const size_t tlds = (size_t)p.lds_per_wave + (2 * 5 * 64 + 2 * (6 * 64 + 4) + 4 + 2 * 64) * sizeof(int);
+                        const size_t tlds = (size_t)p.lds_per_wave + (2 * 5 * 64 + 2 * (5 * 64 + 4) + 4 + 2 * 3 * 64) * sizeof(int);
                         last_waves_per_env = 3;
                         if (inj) WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_PARTIAL, true, true, true, 2>), pgrid, tblock, tlds, st, p);
                         else WURM_LAUNCH((rollout_s9_kernel<WURM_OBS_PARTIAL, false, true, true, 2>), pgrid, tblock, tlds, st, p);

@@ -609,6 +609,42 @@ int wurm_multi_act(const float *params, const float *obs, int64_t *actions, floa
                    int64_t num_envs, int num_snakes, int num_species, int num_inputs, uint64_t seed, uint64_t call,
                    int64_t env_offset, void *stream);
 
+/* wurm_multi_act with a LINE-UP per env: a league of num_policies policies in one batch, every (snake k, env i) row
+ * r = k * num_envs + i played by the policy the caller's lists name (experiments/eval.py: random matchups of agents out
+ * of a folder of checkpoints, one process each there).  Kernel: wurm_amd/csrc/multi_league.hpp.  The arithmetic, the
+ * outputs and the draw of a row are wurm_multi_act's, bit for bit: they do not depend on who plays the other rows.
+ *   params  (>= num_policies, P) fp32, row a as pack_policy_params;  obs, actions, probs, values as for wurm_multi_act
+ *   order   (num_snakes * num_envs) int32, device: the rows sorted by policy
+ *   offsets (num_policies + 1) int64, device: policy a plays the rows order[offsets[a] .. offsets[a + 1]).  Neither is read
+ *           on the host.  The kernel clamps the offsets to [0, num_snakes * num_envs] and skips an entry of `order` outside
+ *           [0, num_snakes * num_envs): it reads and writes in bounds whatever the two hold.  A row no list names is not
+ *           written.  num_policies may exceed num_snakes, and 256; a policy without rows is legal.
+ * Refused before any HIP call: negative sizes, num_policies < 1 and — with num_envs > 0 and num_snakes > 0 — null params,
+ * obs, order, offsets or actions (WURM_ERR_INVALID_ARG); a num_inputs that is not 3 (2n+1)^2 with n <= 6, and
+ * num_snakes * num_envs >= 2^31 (WURM_ERR_UNSUPPORTED).  num_envs = 0 (or num_snakes = 0) is a successful no-op without a
+ * launch.  Otherwise exactly one launch on `stream`, its grid sized from num_snakes, num_envs and num_policies alone; no
+ * atomics. */
+int wurm_multi_act_league(const float *params, const float *obs, const int32_t *order, const int64_t *offsets,
+                          int64_t *actions, float *probs, float *values, int64_t num_envs, int num_snakes,
+                          int num_policies, int num_inputs, uint64_t seed, uint64_t call, int64_t env_offset, void *stream);
+
+/* The per-policy results of one window of such a league, added to a persistent device table.
+ *   rewards (T, R) fp32, dones (T, R) bytes: R = num_rows = num_snakes * num_envs columns k * num_envs + i, T = num_steps
+ *   food, size (T, R) fp32, boost, snake_collision, edge_collision (T, R) bytes: each nullable (its column gets nothing)
+ *   order, offsets: as for wurm_multi_act_league, with the same clamping and skipping
+ *   table   (num_policies, 8) doubles, added to.  Row a, over the rows of policy a and the T steps: [0] steps (row-steps:
+ *           T per row), [1] the sum of rewards, [2] deaths (steps with done set), [3] food, [4] snake_collisions,
+ *           [5] edge_collisions, [6] boost (steps with the flag set), [7] the sum of size.
+ * One workgroup per policy; per thread its list entries in order, then a fixed wave butterfly and the waves in order, in
+ * double: no atomics, the same bits every run (and sums of integers and of rewards in {-1, 0, 1} are exact).
+ * Refused before any HIP call: negative sizes, num_policies < 1 and — with num_rows > 0 and num_steps > 0 — null rewards,
+ * dones, order, offsets or table (WURM_ERR_INVALID_ARG); num_rows >= 2^31 (WURM_ERR_UNSUPPORTED).  num_rows = 0 or
+ * num_steps = 0 is a successful no-op without a launch.  Otherwise exactly one launch on `stream`. */
+int wurm_multi_league_scores(const float *rewards, const uint8_t *dones, const float *food, const float *size,
+                             const uint8_t *boost, const uint8_t *snake_collision, const uint8_t *edge_collision,
+                             const int32_t *order, const int64_t *offsets, double *table, int64_t num_rows,
+                             int64_t num_steps, int num_policies, void *stream);
+
 /* wurm.utils.determine_orientations (wurm/utils.py:36-65) over a (n,3,S,S) batch; out (n) int64. */
 int wurm_orientations(const float *envs, int64_t *out, int64_t n, int size, void *stream);
 

@@ -40,6 +40,7 @@ SYMBOLS = [
     'wurm_multi_rollout_stats_workspace_bytes', 'wurm_multi_rollout_stats',
     'wurm_multi_rollout_frames',
     'wurm_multi_policy_window_plan', 'wurm_multi_policy_window',
+    'wurm_multi_act_league', 'wurm_multi_league_scores',
 ]
 
 

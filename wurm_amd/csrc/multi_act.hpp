@@ -51,6 +51,83 @@ struct MultiActArgs {
 // snakes [k0, k1) of species s: the k with k * P / K == s
 __host__ __device__ inline int multi_act_first_snake(int s, int K, int P) { return (int)(((long long)s * K + P - 1) / P); }
 
+// The three pieces of the kernel that do not depend on how a workgroup finds its rows, written once: multi_act_kernel below
+// walks a consecutive range, multi_act_league_kernel (multi_league.hpp) an index list.
+
+// W1 (64, E) of `params` -> LDS as (EP / 2, 64) pairs, zero padded: input k of unit j at float 128 (k / 2) + 2 j + (k & 1).
+// The whole workgroup; its barrier follows at the caller.
+template <int E>
+__device__ __forceinline__ void multi_act_copy_w1(const float *params)
+{
+    constexpr int EP = (E + 15) & ~15;
+    float *w1f = (float *)wurm_lds;
+    constexpr int n = 64 * E, pad = EP - E;
+#pragma unroll 4
+    for (int i = (int)threadIdx.x; i < n; i += 64 * MULTI_ACT_WAVES) {
+        const int j = i / E, k = i - j * E;
+        w1f[(k >> 1) * 128 + 2 * j + (k & 1)] = params[i];
+    }
+    for (int i = (int)threadIdx.x; i < 64 * pad; i += 64 * MULTI_ACT_WAVES) {
+        const int j = i / pad, k = E + (i - j * pad);
+        w1f[(k >> 1) * 128 + 2 * j + (k & 1)] = 0.0f;
+    }
+}
+
+// the observation of row r from HBM into registers: input lane + 64 i in slot i
+template <int E, int NX>
+__device__ __forceinline__ void multi_act_load_row(float (&xs)[NX], const float *obs, long long r, int lane)
+{
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xs[i] = lane + 64 * i < E ? obs[r * E + lane + 64 * i] : 0.0f;
+}
+
+// ... and from the registers into the wave's LDS row x (EP floats)
+template <int EP, int NX>
+__device__ __forceinline__ void multi_act_stage_row(float *x, const float (&xs)[NX], int lane)
+{
+#pragma unroll
+    for (int i = 0; i < NX; ++i)
+        if (lane + 64 * i < EP) x[lane + 64 * i] = xs[i];
+}
+
+// Row r = k N + i with its observation staged in x: the draw, the first layer against the workgroup's W1 (wl: the lane's
+// column of pairs), the head, and the row's three outputs.  Ends with the wave's LDS fence: x and h1 may be rewritten.
+template <int EP>
+__device__ __forceinline__ void multi_act_row(const MultiActArgs &a, long long r, const float *x, float *h1,
+                                              const PolicyHead::f2 *wl, const PolicyHead &head, int lane)
+{
+    typedef PolicyHead::f2 f2;
+    const long long k = r / a.N, env = r - k * a.N;
+    const u64 env_id = (u64)(a.env_offset + env) * (u64)a.K + (u64)k;
+    const float u = u01(rng_words(a.seed, a.call, env_id, RNG_POLICY, 0).w[0]);
+    wave_lds_sync();
+    // first layer: 16 inputs per batch — 4 broadcast ds_read_b128 of x and 8 ds_read_b64 of weights, then 8 v_pk_fma
+    f2 acc2 = {head.bias1, 0.0f};
+#pragma unroll 2
+    for (int k0 = 0; k0 < EP; k0 += 16) {
+        float4 xv[4];
+        f2 ws[8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) xv[i] = *(const float4 *)(x + k0 + 4 * i);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ws[i] = wl[(k0 / 2 + i) * 64];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const f2 lo = {xv[i].x, xv[i].y}, hi = {xv[i].z, xv[i].w};
+            acc2 = __builtin_elementwise_fma(ws[2 * i], lo, acc2);
+            acc2 = __builtin_elementwise_fma(ws[2 * i + 1], hi, acc2);
+        }
+    }
+    float p0, p1, p2, p3, value;
+    const int act = head.act(acc2, h1, lane, u, p0, p1, p2, p3, value);
+    if (lane == 0) {
+        a.actions[r] = (long long)act;
+        if (a.values) a.values[r] = value;
+    }
+    if (a.probs && lane < 4) a.probs[4 * r + lane] = lane == 0 ? p0 : lane == 1 ? p1 : lane == 2 ? p2 : p3;
+    wave_lds_sync(); // (x and h1 are rewritten for the next row)
+}
+
 template <int NOBS>
 __global__ __launch_bounds__(64 * MULTI_ACT_WAVES)
 void multi_act_kernel(MultiActArgs a)
@@ -63,19 +140,7 @@ void multi_act_kernel(MultiActArgs a)
     const long long stride = (long long)a.wgps * MULTI_ACT_WAVES;
     if (wg_first >= row_end) return; // (the whole workgroup: a species with fewer rows than the largest one)
     const float *params = a.params + (long long)species * policy_num_params(E);
-    {   // W1 (64, E) -> LDS as (EP / 2, 64) pairs, zero padded: input k of unit j at float 128 (k / 2) + 2 j + (k & 1)
-        float *w1f = (float *)wurm_lds;
-        constexpr int n = 64 * E, pad = EP - E;
-#pragma unroll 4
-        for (int i = (int)threadIdx.x; i < n; i += 64 * MULTI_ACT_WAVES) {
-            const int j = i / E, k = i - j * E;
-            w1f[(k >> 1) * 128 + 2 * j + (k & 1)] = params[i];
-        }
-        for (int i = (int)threadIdx.x; i < 64 * pad; i += 64 * MULTI_ACT_WAVES) {
-            const int j = i / pad, k = E + (i - j * pad);
-            w1f[(k >> 1) * 128 + 2 * j + (k & 1)] = 0.0f;
-        }
-    }
+    multi_act_copy_w1<E>(params);
     __syncthreads();
     const int wave = uniform((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
     long long r = wg_first + wave;
@@ -86,46 +151,12 @@ void multi_act_kernel(MultiActArgs a)
     head.load(params, E, lane);
 
     float xs[NX]; // the row's observation, input lane + 64 i in slot i
-#pragma unroll
-    for (int i = 0; i < NX; ++i) xs[i] = lane + 64 * i < E ? a.obs[r * E + lane + 64 * i] : 0.0f;
+    multi_act_load_row<E>(xs, a.obs, r, lane);
     for (; r < row_end; r += stride) {
-#pragma unroll
-        for (int i = 0; i < NX; ++i)
-            if (lane + 64 * i < EP) x[lane + 64 * i] = xs[i];
+        multi_act_stage_row<EP>(x, xs, lane);
         const long long next = r + stride;
-        if (next < row_end) {
-#pragma unroll
-            for (int i = 0; i < NX; ++i) xs[i] = lane + 64 * i < E ? a.obs[next * E + lane + 64 * i] : 0.0f;
-        }
-        const long long k = r / a.N, env = r - k * a.N;
-        const u64 env_id = (u64)(a.env_offset + env) * (u64)a.K + (u64)k;
-        const float u = u01(rng_words(a.seed, a.call, env_id, RNG_POLICY, 0).w[0]);
-        wave_lds_sync();
-        // first layer: 16 inputs per batch — 4 broadcast ds_read_b128 of x and 8 ds_read_b64 of weights, then 8 v_pk_fma
-        f2 acc2 = {head.bias1, 0.0f};
-#pragma unroll 2
-        for (int k0 = 0; k0 < EP; k0 += 16) {
-            float4 xv[4];
-            f2 ws[8];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) xv[i] = *(const float4 *)(x + k0 + 4 * i);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) ws[i] = wl[(k0 / 2 + i) * 64];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const f2 lo = {xv[i].x, xv[i].y}, hi = {xv[i].z, xv[i].w};
-                acc2 = __builtin_elementwise_fma(ws[2 * i], lo, acc2);
-                acc2 = __builtin_elementwise_fma(ws[2 * i + 1], hi, acc2);
-            }
-        }
-        float p0, p1, p2, p3, value;
-        const int act = head.act(acc2, h1, lane, u, p0, p1, p2, p3, value);
-        if (lane == 0) {
-            a.actions[r] = (long long)act;
-            if (a.values) a.values[r] = value;
-        }
-        if (a.probs && lane < 4) a.probs[4 * r + lane] = lane == 0 ? p0 : lane == 1 ? p1 : lane == 2 ? p2 : p3;
-        wave_lds_sync(); // (x and h1 are rewritten for the next row)
+        if (next < row_end) multi_act_load_row<E>(xs, a.obs, next, lane);
+        multi_act_row<EP>(a, r, x, h1, wl, head, lane);
     }
 }
 

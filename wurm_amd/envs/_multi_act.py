@@ -67,8 +67,8 @@ def _num_inputs(env) -> int:
     return 3 * (2 * n + 1) ** 2
 
 
-def _params(env, params, num_species, E):
-    """(params, num_species) checked"""
+def _param_rows(env, params, E) -> int:
+    """`params` checked but for how many rows it needs (`_params`, `_multi_league`): the rows it has"""
     if not isinstance(params, torch.Tensor):
         raise RuntimeError(f'MultiSnake.act: params must be a tensor, got {type(params).__name__}')
     if params.dtype != torch.float32:
@@ -83,7 +83,12 @@ def _params(env, params, num_species, E):
         raise _lib.WurmHipError(f'MultiSnake.act runs on the GPU: params is on {params.device}. There is no CPU fallback.')
     if params.device != env.device:
         raise RuntimeError(f'MultiSnake.act: params is on {params.device}, the env on {env.device}')
-    rows = params.shape[0] if params.dim() == 2 else 1
+    return params.shape[0] if params.dim() == 2 else 1
+
+
+def _params(env, params, num_species, E):
+    """(params, num_species) checked"""
+    rows = _param_rows(env, params, E)
     if num_species is None:
         num_species = rows
     num_species = int(num_species)
@@ -132,29 +137,38 @@ def _observations(env, observations, E):
     return torch.stack([v.reshape(N, E) for v in vals]), N
 
 
+def _outputs(env, N, out):
+    """(actions (K, N) int64, probs (K, N, 4), values (K, N)) for the kernel to write: `out` (a window's rows) or fresh"""
+    K, dev = env.num_snakes, env.device
+    if out is None:
+        return (torch.empty((K, N), dtype=torch.long, device=dev), torch.empty((K, N, 4), dtype=torch.float32, device=dev),
+                torch.empty((K, N), dtype=torch.float32, device=dev))
+    if out[0].shape != (K, N):  # (the window's rows are sized for the env's own batch)
+        raise RuntimeError(f'MultiSnake.act_window: observations of {N} envs for an env object of {out[0].shape[1]}')
+    return out
+
+
+def _acted(env, actions, probs, values) -> dict:
+    """what `act` returns, behind its launch"""
+    env.policy_calls += 1
+    # (a plain dict of the K rows of one (K, N) int64 block: what the step machine launches on without stacking)
+    return {'actions': {f'agent_{k}': a for k, a in enumerate(actions.unbind(0))}, 'actions_t': actions, 'probs': probs,
+            'values': values}
+
+
 def act(env, params, observations, num_species=None, out=None) -> dict:
     """MultiSnake.act.  out: (actions (K, N) int64, probs (K, N, 4), values (K, N)) to write into (act_window's rows)."""
     E = _num_inputs(env)
     params, P = _params(env, params, num_species, E)
     obs, N = _observations(env, observations, E)
     K, dev = env.num_snakes, env.device
-    if out is None:
-        actions = torch.empty((K, N), dtype=torch.long, device=dev)
-        probs = torch.empty((K, N, 4), dtype=torch.float32, device=dev)
-        values = torch.empty((K, N), dtype=torch.float32, device=dev)
-    else:
-        actions, probs, values = out
-        if actions.shape != (K, N):  # (the window's rows are sized for the env's own batch)
-            raise RuntimeError(f'MultiSnake.act_window: observations of {N} envs for an env object of {actions.shape[1]}')
+    actions, probs, values = _outputs(env, N, out)
     ptr = _lib.ptr
     rc = _lib.call(dev.index, _lib.lib().wurm_multi_act, ptr(params), ptr(obs), ptr(actions), ptr(probs), ptr(values),
                    _lib.i64(N), K, P, E, _lib.u64(env.seed), _lib.u64(env.policy_calls), _lib.i64(env.env_offset),
                    _lib.stream_ptr(dev.index))
     _lib.check(rc, 'MultiSnake.act')
-    env.policy_calls += 1
-    # (a plain dict of the K rows of one (K, N) int64 block: what the step machine launches on without stacking)
-    return {'actions': {f'agent_{k}': a for k, a in enumerate(actions.unbind(0))}, 'actions_t': actions, 'probs': probs,
-            'values': values}
+    return _acted(env, actions, probs, values)
 
 
 # the keys `act_window(..., info=True)` adds: (name, prefix of the step's info key, dtype)
@@ -162,19 +176,25 @@ INFO_KEYS = (('food', 'food_', torch.float32), ('size', 'size_', torch.float32),
              ('snake_collision', 'snake_collision_', torch.bool), ('edge_collision', 'edge_collision_', torch.bool))
 
 
-def act_window(env, params, state, num_steps, num_species=None, info=False) -> dict:
-    """MultiSnake.act_window"""
+def act_window(env, params, state, num_steps, num_species=None, info=False, acting=None) -> dict:
+    """MultiSnake.act_window.  acting: `acting(state, out)` in place of `act(env, params, state, num_species, out)` — the
+    acting call of another binding of policies to rows (`_multi_league.league_window`), which has checked its own
+    arguments; stepping, resetting and gathering are the same."""
     T, K, N, dev = int(num_steps), env.num_snakes, env.num_envs, env.device
     if T < 0:
         raise RuntimeError(f'MultiSnake.act_window: num_steps must not be negative, got {T}')
     E = _num_inputs(env)
+    if acting is None:
+        acting = lambda state, out: act(env, params, state, num_species, out)
+        if T == 0:
+            _params(env, params, num_species, E)
     actions = torch.empty((T, K * N), dtype=torch.long, device=dev)
     probs = torch.empty((T, K * N, 4), dtype=torch.float32, device=dev)
     values = torch.empty((T, K * N), dtype=torch.float32, device=dev)
     keys = [f'agent_{k}' for k in range(K)]
     obs_rows, reward_rows, done_rows, all_rows, infos = [], [], [], [], []
     for t in range(T):
-        a = act(env, params, state, num_species, (actions[t].view(K, N), probs[t].view(K, N, 4), values[t].view(K, N)))
+        a = acting(state, (actions[t].view(K, N), probs[t].view(K, N, 4), values[t].view(K, N)))
         obs, rewards, dones, step_info = env.step(a['actions'])
         env.reset(dones['__all__'], return_observations=False)
         if info:
@@ -186,7 +206,6 @@ def act_window(env, params, state, num_steps, num_species=None, info=False) -> d
         all_rows.append(dones['__all__'])
         state = obs
     if T == 0:
-        _params(env, params, num_species, E)
         observations = torch.empty((0, K * N, E), dtype=torch.float32, device=dev)
         rewards_t = torch.empty((0, K * N), dtype=torch.float32, device=dev)
         dones_t = torch.empty((0, K * N), dtype=torch.bool, device=dev)

@@ -907,6 +907,38 @@ class MultiSnake(object):
         from wurm_amd.envs import _multi_policy_window
         return _multi_policy_window.plan(self, num_species) != 0
 
+    # ------------------------------------------------------------------ a league: a line-up per env (extension;
+    # wurm_amd/envs/_multi_league.py)
+
+    def league_plan(self, lineup: torch.Tensor, num_policies: int):
+        """The row lists `act_league` / `league_window` / `wurm_amd.rl.LeagueTable.update` run on, once per draw of
+        matchups.  lineup: (num_snakes, num_envs) integer tensor, `lineup[k, i]` the row of `params` that plays snake k of
+        env i, each in [0, num_policies) — any policy any number of times, also twice in one env, also never.  Returns a
+        `LeaguePlan(lineup, order, offsets, num_policies)`: `order` (K N) int32, the rows k * N + i sorted by policy (stable:
+        ascending within a policy), `offsets` (num_policies + 1) int64 — torch ops on `lineup`'s device (a CPU line-up
+        gives a CPU plan, which no launch takes).  One host synchronisation, the range check; RuntimeError for a wrong
+        shape or dtype and for an entry outside [0, num_policies)."""
+        from wurm_amd.envs import _multi_league
+        return _multi_league.league_plan(self, lineup, num_policies)
+
+    def act_league(self, params: torch.Tensor, observations, plan) -> dict:
+        """`act` with the policy of every (snake, env) row taken from `plan` (the reference's experiments/eval.py plays
+        one matchup per process): one launch, no host synchronisation, the dict of `act`.  params: (A, num_params) fp32
+        with at least `plan.num_policies` rows, checked as `act` checks them; A may exceed num_snakes.  observations: as
+        for `act`.  A row's probs, value and action are those `act` gives that row under the same policy — they do not
+        depend on the other rows' line-up.  `policy_calls` grows by one; the env's own counter, its state and a postponed
+        reset are left alone.  'partial_n' with n <= 6 and dtype=torch.float only (NotImplementedError otherwise)."""
+        from wurm_amd.envs import _multi_league
+        return _multi_league.act_league(self, params, observations, plan)
+
+    def league_window(self, params: torch.Tensor, state, num_steps: int, plan, info: bool = False) -> dict:
+        """`act_window` with `act_league(params, state, plan)` as its acting call: the same keys, shapes and columns
+        k * N + i, two launches per step; `record_start` / `record_frames` take its `actions`, `LeagueTable.update` the
+        whole dict.  Not fused into one launch, and not a layout `FusedA2CPopulation.update` takes (a policy's columns are
+        wherever the line-up put them): the league plays and scores."""
+        from wurm_amd.envs import _multi_league
+        return _multi_league.league_window(self, params, state, num_steps, plan, info)
+
     # ------------------------------------------------------------------ frames of a fused window (extension;
     # wurm_amd/envs/_multi_frames.py)
 

@@ -803,6 +803,72 @@ int wurm_a2c_ff_pop_update_gae(float *params, const float *obs0, const float *ob
                                float *exp_avg, float *exp_avg_sq, float *grad_norm, int64_t step, float beta1,
                                float beta2, float eps, float max_grad_norm, void *stream, float *returns_out);
 
+/* ------------------------------------------------------------------------------------------- fused A2C league
+ * The population calls for a LEAGUE: member a learns from an index list of columns of any length instead of a consecutive
+ * block of num_envs / num_members.  The (T, R, .) inputs are a MultiSnake window of R = num_rows = num_snakes * num_envs
+ * columns k * num_envs + i (obs0 (R, E) the observations it started from), and
+ *   order   (R) int32, DEVICE;  offsets (num_members + 1) int64, DEVICE: member a owns the columns
+ *           order[offsets[a] .. offsets[a + 1]), M_a of them — what MultiSnake.league_plan makes for wurm_multi_act_league.
+ *           Neither is read on the host.
+ *   learn   (num_members) bytes, DEVICE, nullable: learn[a] == 0 keeps member a out of this update.
+ * Still three launches, sized from R and num_members alone: (min(R, 256), num_members) workgroups for the main kernel.
+ * Member a's workgroups form M_a, G_a = min(M_a, 256) and 1 / (M_a T) from `offsets` themselves; those with
+ * blockIdx.x >= G_a return at once.  Member a's sub-grid then has the workgroups, ranges (over LIST POSITIONS), tile order
+ * and summation order of a stand-alone call with num_envs = M_a, so every result of member a is bit for bit that call's on
+ * contiguous copies of its columns taken in list order (means over its own M_a T samples).
+ *   A member with learn[a] == 0 or M_a == 0: its rows of params, exp_avg and exp_avg_sq are not touched, its rows of grad
+ *   and losses and its grad_norm are written as zeros, and its columns of values_out / returns_out are not written (nor
+ *   is any column that no list names): the caller zeroes the two beforehand.  `step` is shared by all members as in the
+ *   population, so a member that sat windows out is stepped with the bias corrections of the shared count.
+ *   Bounds: the kernels clamp the offsets to [0, R] and make them non-decreasing (a running maximum), and give an entry of
+ *   `order` outside [0, R) a row with zero input and zero loss derivative (it still counts in M_a): they read and write in
+ *   bounds whatever the two arrays hold.
+ *   hyper, beta1, beta2, eps, max_grad_norm, value_loss_kind: as for the population.
+ * Refused before any HIP call: null pointers (learn and the optional outputs aside), num_members <= 0, num_rows <= 0, a
+ * workspace that is too small or not 16-byte aligned (WURM_ERR_INVALID_ARG); more than 65535 members, num_rows >= 2^31
+ * (WURM_ERR_UNSUPPORTED); and whatever the stand-alone call refuses for num_steps, num_inputs and value_loss_kind. */
+
+/* Bytes of the workspace, from host-known bounds: min(num_rows, 256 * num_members) partial gradients (member a's
+ * min(M_a, 256) start at group index sum over b < a of min(M_b, 256), which its workgroups and the reduce kernel form from
+ * `offsets`), then eight parked floats for each of the num_rows * (num_steps + 1) rows, by list position.  0 for an
+ * unsupported shape. */
+int64_t wurm_a2c_ff_league_workspace_bytes(int64_t num_rows, int64_t num_steps, int num_inputs, int64_t num_members);
+
+int wurm_a2c_ff_league_grad(const float *params, const float *obs0, const float *obs, const int64_t *actions,
+                            const float *rewards, const uint8_t *dones, const double *hyper, const int32_t *order,
+                            const int64_t *offsets, const uint8_t *learn, int value_loss_kind, float *grad,
+                            float *losses, float *values_out, void *workspace, int64_t workspace_bytes,
+                            int64_t num_rows, int64_t num_steps, int num_inputs, int64_t num_members, void *stream);
+
+int wurm_a2c_ff_league_grad_gae(const float *params, const float *obs0, const float *obs, const int64_t *actions,
+                                const float *rewards, const uint8_t *dones, const double *hyper, const int32_t *order,
+                                const int64_t *offsets, const uint8_t *learn, int value_loss_kind, float *grad,
+                                float *losses, float *values_out, void *workspace, int64_t workspace_bytes,
+                                int64_t num_rows, int64_t num_steps, int num_inputs, int64_t num_members, void *stream,
+                                float *returns_out);
+
+/* num_params: of ONE member; offsets, learn and num_rows say who steps (the lists themselves are not needed). */
+int wurm_a2c_ff_league_apply(float *params, const float *grad, float *exp_avg, float *exp_avg_sq, float *grad_norm,
+                             const double *hyper, const int64_t *offsets, const uint8_t *learn, int64_t step,
+                             float beta1, float beta2, float eps, float max_grad_norm, int64_t num_params,
+                             int64_t num_rows, int64_t num_members, void *stream);
+
+int wurm_a2c_ff_league_update(float *params, const float *obs0, const float *obs, const int64_t *actions,
+                              const float *rewards, const uint8_t *dones, const double *hyper, const int32_t *order,
+                              const int64_t *offsets, const uint8_t *learn, int value_loss_kind, float *grad,
+                              float *losses, float *values_out, void *workspace, int64_t workspace_bytes,
+                              int64_t num_rows, int64_t num_steps, int num_inputs, int64_t num_members, float *exp_avg,
+                              float *exp_avg_sq, float *grad_norm, int64_t step, float beta1, float beta2, float eps,
+                              float max_grad_norm, void *stream);
+
+int wurm_a2c_ff_league_update_gae(float *params, const float *obs0, const float *obs, const int64_t *actions,
+                                  const float *rewards, const uint8_t *dones, const double *hyper, const int32_t *order,
+                                  const int64_t *offsets, const uint8_t *learn, int value_loss_kind, float *grad,
+                                  float *losses, float *values_out, void *workspace, int64_t workspace_bytes,
+                                  int64_t num_rows, int64_t num_steps, int num_inputs, int64_t num_members,
+                                  float *exp_avg, float *exp_avg_sq, float *grad_norm, int64_t step, float beta1,
+                                  float beta2, float eps, float max_grad_norm, void *stream, float *returns_out);
+
 /* Population-based training, the exploit / explore step, in two launches on `stream` (kernels: wurm_amd/csrc/a2c_pbt.hpp):
  * no atomics, no grid-wide barrier, nothing read back.
  *   scores  DEVICE (num_members) doubles, only read; a NaN counts as -infinity.  rank(p) = #{q : score_q > score_p or

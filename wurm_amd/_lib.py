@@ -41,6 +41,8 @@ SYMBOLS = [
     'wurm_multi_rollout_frames',
     'wurm_multi_policy_window_plan', 'wurm_multi_policy_window',
     'wurm_multi_act_league', 'wurm_multi_league_scores',
+    'wurm_a2c_ff_league_workspace_bytes', 'wurm_a2c_ff_league_grad', 'wurm_a2c_ff_league_grad_gae',
+    'wurm_a2c_ff_league_apply', 'wurm_a2c_ff_league_update', 'wurm_a2c_ff_league_update_gae',
 ]
 
 

@@ -4,6 +4,7 @@
 //   a2c_ff_reduce_kernel  sums the workgroups' partials in workgroup order into grad / losses
 //   a2c_ff_apply_kernel   ||g|| in a fixed order (every workgroup computes the same bits), clip, Adam
 // and the three with a member dimension in the grid (a2c_ff_main_kernel<GAE, true>, a2c_ff_*_pop_kernel): P updates at once
+// and with an index list of columns per member (a2c_ff_main_kernel<GAE, false, true>, a2c_ff_*_league_kernel): a league
 // No float atomics anywhere: two runs on the same inputs give the same bits.
 //
 // Main kernel.  A workgroup (256 threads) owns the envs [wg N / G, (wg + 1) N / G) with all T + 1 rows of each (the T
@@ -82,8 +83,58 @@ template <class Base> struct PopArgs : Base {
     long long M;
 };
 
-template <bool GAE, bool POP> struct kernel_args { using type = typename main_args<GAE>::type; };
-template <bool GAE> struct kernel_args<GAE, true> { using type = PopArgs<typename main_args<GAE>::type>; };
+// ---- league: the population with an INDEX LIST where it has a consecutive block.  Member a learns from
+// the columns order[offsets[a] .. offsets[a + 1]) of the (T, N, .) tensors, N = K N_envs rows of a MultiSnake window, as
+// MultiSnake.league_plan lays the two out (multi_league.hpp).  Nothing about the lists is known on the host: the grid is
+// (min(N, 256), A) and member a's workgroups size themselves — M_a, G_a = min(M_a, 256), inv_B — from `offsets`, so
+// that its part of the grid is again the grid of a stand-alone update of its M_a columns in list order.  Everything
+// indexed by env goes through the list; the parked rows and the partials are indexed by list position.
+template <class Base> struct LeagueArgs : Base { // N: all rows; G: the grid's x (an upper bound of every G_a)
+    const double *hyper;        // (A, HYPER_DOUBLES)
+    const int *order;           // (N)
+    const long long *offsets;   // (A + 1)
+    const uint8_t *learn;       // (A), nullable: 0 = this member sits the update out
+};
+
+// What member a of a league owns.  The offsets are clamped to [0, N] and made non-decreasing (a running maximum), so the
+// members' lists are disjoint pieces of `order` whatever `offsets` holds: first + M <= N, and the M of all members sum
+// to at most N.  `base` is the group index of the member's first partial, sum over b < a of min(M_b, 256): sums of
+// integers, the same in every workgroup and kernel.  (A serial walk over a + 1 offsets per workgroup, all of it scalar.)
+struct LeagueMember {
+    long long first, M, base;
+    int G;       // min(M, 256)
+    float inv_B; // 1 / (M T), rounded as the host rounds 1.0f / (float)(M T)
+};
+
+__device__ __forceinline__ LeagueMember league_member(const long long *__restrict__ offsets, long long a, long long N,
+                                                      long long T)
+{
+    LeagueMember m;
+    long long lo = offsets[0];
+    lo = lo < 0 ? 0 : (lo > N ? N : lo);
+    m.base = 0;
+    for (long long b = 0; b < a; ++b) {
+        long long hi = offsets[b + 1];
+        hi = hi < lo ? lo : (hi > N ? N : hi);
+        m.base += hi - lo < MAX_GROUPS ? hi - lo : MAX_GROUPS;
+        lo = hi;
+    }
+    long long hi = offsets[a + 1];
+    hi = hi < lo ? lo : (hi > N ? N : hi);
+    m.first = lo;
+    m.M = hi - lo;
+    m.G = (int)(m.M < MAX_GROUPS ? m.M : MAX_GROUPS);
+    // The host forms 1.0f / (float)(M T), one correctly rounded fp32 division.  Here the quotient is taken in double and
+    // rounded to float: the reciprocal of a 24-bit number is either exact (a power of two) or at least 2^-49 of itself
+    // away from every 25-bit number, so the double quotient never sits on a float rounding boundary and the second
+    // rounding gives the correctly rounded fp32 quotient — whatever the fp32 division of the build expands to.
+    m.inv_B = (float)(1.0 / (double)(float)(m.M * T));
+    return m;
+}
+
+template <bool GAE, bool POP, bool LEAGUE = false> struct kernel_args { using type = typename main_args<GAE>::type; };
+template <bool GAE> struct kernel_args<GAE, true, false> { using type = PopArgs<typename main_args<GAE>::type>; };
+template <bool GAE> struct kernel_args<GAE, false, true> { using type = LeagueArgs<typename main_args<GAE>::type>; };
 
 // acc[i][j] += sum_k A[4 tr + i][k] * B[tj + 16 j][k], k < K (a multiple of 4)
 __device__ __forceinline__ void gemm_nt(const float *A, const float *B, int K, int tr, int tj, float (&acc)[4][4])
@@ -142,8 +193,8 @@ __device__ __forceinline__ float value_loss_derivative(int loss_kind, float dl)
     return 2.0f * dl; // squared error
 }
 
-template <bool GAE, bool POP = false>
-__global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(typename kernel_args<GAE, POP>::type g)
+template <bool GAE, bool POP = false, bool LEAGUE = false>
+__global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(typename kernel_args<GAE, POP, LEAGUE>::type g)
 {
     __shared__ __attribute__((aligned(16))) float Xs[TILE * LD], W1s[HID * LD], W2s[HID * LD], W2Ts[HID * LD];
     __shared__ __attribute__((aligned(16))) float H1s[TILE * LD], H2s[TILE * LD], dZ2s[TILE * LD], dZ1s[TILE * LD];
@@ -173,10 +224,30 @@ __global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(typename kernel_ar
             if (g.returns_out != nullptr) g.returns_out += first;
         }
     }
+    const int *order = nullptr; // LEAGUE: the member's list; list position i is column order[i] of the inputs
+    long long listed = 0;       // LEAGUE: M_a
+    if constexpr (LEAGUE) { // this member's list, weights, workspace and hyper-parameters, sized here from `offsets`
+        const long long m = blockIdx.y;
+        const LeagueMember mem = league_member(g.offsets, m, g.N, g.T);
+        // nothing to learn from, told to sit out, or a workgroup past this member's G_a: gone before LDS is touched
+        if (mem.M == 0 || (g.learn != nullptr && g.learn[m] == 0) || (long long)blockIdx.x >= mem.G) return;
+        g.params += m * num_params(g.E);
+        g.partials += mem.base * partial_stride(g.E);
+        g.rows += mem.first * (g.T + 1) * ROW_FLOATS;
+        g.G = mem.G;
+        g.inv_B = mem.inv_B;
+        order = g.order + mem.first; // (first + M <= N: every read of it stays inside the N entries)
+        listed = mem.M;
+        const double *h = g.hyper + m * HYPER_DOUBLES;
+        g.gamma = (float)h[1];
+        g.entropy_coef = (float)h[2];
+        if constexpr (GAE) g.gamma_lambda = (float)h[3];
+    }
     const long long N = g.N, T = g.T; // N: envs per row of the inputs
     const int E = g.E, Epad = padded_inputs(E);
     long long owned; // the envs the grid's x shares out: all N, or the member's M
     if constexpr (POP) owned = g.M;
+    else if constexpr (LEAGUE) owned = listed;
     else owned = N;
     const long long e0 = (long long)blockIdx.x * owned / g.G, e1 = ((long long)blockIdx.x + 1) * owned / g.G;
     const long long nenv = e1 - e0, rows = nenv * (T + 1), ntiles = (rows + TILE - 1) / TILE;
@@ -223,7 +294,11 @@ __global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(typename kernel_ar
             if (lr < rows) {
                 t = lr / nenv;
                 env = e0 + (lr - t * nenv);
-                x = t == 0 ? g.obs0 + env * E : g.obs + ((t - 1) * N + env) * E;
+                if constexpr (LEAGUE) {
+                    env = order[env];
+                    if (env < 0 || env >= N) env = -1; // not a column: zero input, no loss term, nothing read or written
+                }
+                if (!LEAGUE || env >= 0) x = t == 0 ? g.obs0 + env * E : g.obs + ((t - 1) * N + env) * E;
             }
             row_x[tid] = x;
             row_env[tid] = env;
@@ -296,7 +371,8 @@ __global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(typename kernel_ar
             float *o = parked + (tile * TILE + tid) * ROW_FLOATS;
             *reinterpret_cast<float4 *>(o) = make_float4(x0 / sum, x1 / sum, x2 / sum, x3 / sum);
             o[4] = v;
-            if (g.values_out != nullptr && row_t[tid] < T) g.values_out[row_t[tid] * N + row_env[tid]] = v;
+            if (g.values_out != nullptr && row_t[tid] < T && (!LEAGUE || row_env[tid] >= 0))
+                g.values_out[row_t[tid] * N + row_env[tid]] = v;
         }
     }
     __threadfence_block();
@@ -304,7 +380,11 @@ __global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(typename kernel_ar
 
     // ---------------------------------------------------------------- return scan (rl.hip: a2c_returns_kernel)
     for (long long i = tid; i < nenv; i += THREADS) {
-        const long long env = e0 + i;
+        long long env = e0 + i;
+        if constexpr (LEAGUE) {
+            env = order[env];
+            if (env < 0 || env >= N) continue; // (pass 2 does not read what this would have parked)
+        }
         if constexpr (GAE) {
             // backwards: delta_t = r_t + gamma v_{t+1} nd_t - v_t, gae_t = delta_t + gamma_lambda nd_t gae_{t+1}, R = gae + v
             float gae = 0.0f, next = parked[(T * nenv + i) * ROW_FLOATS + 4];
@@ -357,7 +437,7 @@ __global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(typename kernel_ar
             float d[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
             float rv = 0.0f, rp = 0.0f, re = 0.0f;
             const long long t = row_t[tid];
-            if (t >= 0 && t < T) {
+            if (t >= 0 && t < T && (!LEAGUE || row_env[tid] >= 0)) {
                 const float *o = parked + (tile * TILE + tid) * ROW_FLOATS;
                 const float p[4] = {o[0], o[1], o[2], o[3]};
                 const float v = o[4], R = o[5];
@@ -518,6 +598,25 @@ __global__ __launch_bounds__(THREADS) void a2c_ff_reduce_pop_kernel(const float 
     a2c_ff_reduce_body(partials + m * G * partial_stride(E), G, E, inv_B, grad + m * num_params(E), losses + 3 * m);
 }
 
+// league member blockIdx.y: its G_a partials, found and sized by league_member as the main kernel found them -> its row of
+// grad and of losses.  A member that did not learn (no columns, or learn[a] == 0) wrote no partials: its rows are zeros.
+__global__ __launch_bounds__(THREADS) void a2c_ff_reduce_league_kernel(const float *__restrict__ partials,
+                                                                       const long long *__restrict__ offsets,
+                                                                       const uint8_t *__restrict__ learn, long long N,
+                                                                       long long T, int E, float *__restrict__ grad,
+                                                                       float *__restrict__ losses)
+{
+    const long long m = blockIdx.y, P = num_params(E);
+    const LeagueMember mem = league_member(offsets, m, N, T);
+    if (mem.M == 0 || (learn != nullptr && learn[m] == 0)) {
+        const long long i = (long long)blockIdx.x * THREADS + threadIdx.x;
+        if (i < P) grad[m * P + i] = 0.0f;
+        else if (i < P + 3) losses[3 * m + (i - P)] = 0.0f;
+        return;
+    }
+    a2c_ff_reduce_body(partials + mem.base * partial_stride(E), mem.G, E, mem.inv_B, grad + m * P, losses + 3 * m);
+}
+
 constexpr int APPLY_PER_BLOCK = 4 * THREADS;
 
 // Every workgroup forms sum g^2 over ALL of grad in the same order (so they all hold the same bits), then clips and
@@ -583,6 +682,29 @@ __global__ __launch_bounds__(THREADS) void a2c_ff_apply_pop_kernel(float *__rest
                                                                    float eps, float max_norm, long long P)
 {
     const long long m = blockIdx.y, o = m * P;
+    const float step_size = (float)(hyper[m * HYPER_DOUBLES] / bc1);
+    a2c_ff_apply_body(params + o, grad + o, exp_avg + o, exp_avg_sq + o, grad_norm != nullptr ? grad_norm + m : nullptr,
+                      step_size, bc2_sqrt, beta2, w1, w2, eps, max_norm, P);
+}
+
+// the same for a league: a member that did not learn (as the reduce kernel decides it) keeps its rows of params, exp_avg
+// and exp_avg_sq bit for bit — an Adam step on a zero gradient would still move them — and gets grad_norm = 0
+__global__ __launch_bounds__(THREADS) void a2c_ff_apply_league_kernel(float *__restrict__ params,
+                                                                      const float *__restrict__ grad,
+                                                                      float *__restrict__ exp_avg,
+                                                                      float *__restrict__ exp_avg_sq,
+                                                                      float *__restrict__ grad_norm,
+                                                                      const double *__restrict__ hyper,
+                                                                      const long long *__restrict__ offsets,
+                                                                      const uint8_t *__restrict__ learn, long long N,
+                                                                      double bc1, float bc2_sqrt, float beta2, float w1,
+                                                                      float w2, float eps, float max_norm, long long P)
+{
+    const long long m = blockIdx.y, o = m * P;
+    if (league_member(offsets, m, N, 1).M == 0 || (learn != nullptr && learn[m] == 0)) {
+        if (blockIdx.x == 0 && threadIdx.x == 0 && grad_norm != nullptr) grad_norm[m] = 0.0f;
+        return;
+    }
     const float step_size = (float)(hyper[m * HYPER_DOUBLES] / bc1);
     a2c_ff_apply_body(params + o, grad + o, exp_avg + o, exp_avg_sq + o, grad_norm != nullptr ? grad_norm + m : nullptr,
                       step_size, bc2_sqrt, beta2, w1, w2, eps, max_norm, P);

@@ -15,9 +15,16 @@ as a list: `league_plan` sorts the K N rows by policy once per draw of matchups 
 policy) into `order` (K N) int32 and `offsets` (A + 1) int64.  Both stay on the device and no later call reads them on the
 host: the launch is sized from K, N and A alone.
 
+Learning.  `FusedA2CPopulation.update(state, out, plan=plan, learn=None)` (wurm_amd/rl/fused_population.py;
+include/wurm_hip.h: wurm_a2c_ff_league_*) takes a `league_window` and its plan: policy a learns from the columns
+`order[offsets[a] : offsets[a + 1]]`, however many, in the three launches of one update, bit for bit as a
+`FusedA2CLearner` would from copies of those columns.  `learn` masks policies out (a pool of frozen checkpoints); they and
+policies without rows keep their weights and Adam state.
+
 What is not here.  `policy_window` is not fused for line-ups (`league_window` makes two launches per step, like
-`act_window`).  `FusedA2CPopulation.update` needs the columns of a species consecutive, which a general line-up does not
-give: the league is for playing and scoring (`wurm_amd.rl.LeagueTable`), not for learning.
+`act_window`).  The learner's `step` is shared by the policies: one that sat windows out is stepped with the bias
+corrections of the shared count.  Both the acting and the learning grid are sized by A, not by rows per policy, so a skewed
+line-up leaves workgroups idle while the largest policy's work.
 """
 import operator
 from collections import namedtuple

@@ -934,8 +934,8 @@ class MultiSnake(object):
     def league_window(self, params: torch.Tensor, state, num_steps: int, plan, info: bool = False) -> dict:
         """`act_window` with `act_league(params, state, plan)` as its acting call: the same keys, shapes and columns
         k * N + i, two launches per step; `record_start` / `record_frames` take its `actions`, `LeagueTable.update` the
-        whole dict.  Not fused into one launch, and not a layout `FusedA2CPopulation.update` takes (a policy's columns are
-        wherever the line-up put them): the league plays and scores."""
+        whole dict, and `FusedA2CPopulation.update(state, out, plan=plan)` learns from it (every policy from the columns
+        the line-up put it in).  Not fused into one launch."""
         from wurm_amd.envs import _multi_league
         return _multi_league.league_window(self, params, state, num_steps, plan, info)
 

@@ -32,7 +32,9 @@ class _FusedA2C(object):
     """What FusedA2CLearner and FusedA2CPopulation (fused_population.py) share: the constructor's refusals, the packing of
     the agents into one buffer, the checks of a rollout window, the output tensors and the marshalling of the three calls.
     A subclass says which entry points it calls (`_ENTRY`), how its hyper-parameters are kept (`_own`) and cross the ABI
-    (`_loss_args`, `_step_args`, `_gae_args`), and what one agent's part of `losses` and `grad_norm` is."""
+    (`_loss_args`, `_step_args`, `_gae_args`), and what one agent's part of `losses` and `grad_norm` is.
+    `league` is None everywhere but in FusedA2CPopulation's calls with a plan: there it is the checked
+    (order, offsets, learn) of the line-up, and the calls go to the `wurm_a2c_ff_league_` entry points."""
     _ENTRY = None       # 'wurm_a2c_ff_' or 'wurm_a2c_ff_pop_'
     _WHOSE = None       # 'agent' / 'agents', for the messages
     _LOSS_INDEX = None  # the three indices into `losses` that give value_loss, policy_loss and entropy
@@ -66,7 +68,10 @@ class _FusedA2C(object):
 
     # ------------------------------------------------------------------ plumbing
 
-    def _inputs(self, state, out):
+    def _entry(self, league):
+        return self._ENTRY if league is None else 'wurm_a2c_ff_league_'
+
+    def _inputs(self, state, out, league=None):
         dev, E = self.params.device, self.num_inputs
         if dev.type != 'cuda':
             raise _lib.WurmHipError(f'{type(self).__name__}.grad / update run on the GPU: move the {self._WHOSE} to the '
@@ -75,7 +80,10 @@ class _FusedA2C(object):
         if rewards.dim() != 2 or rewards.numel() == 0:
             raise RuntimeError('rewards must be a non-empty (num_steps, num_envs) tensor')
         T, N = rewards.shape
-        self._check_envs(N)
+        if league is None:
+            self._check_envs(N)
+        else:
+            self._check_league(N, league)
         for name, t in (('state', state), ('observations', obs), ('actions', actions), ('rewards', rewards),
                         ('dones', dones)):
             if t.device != dev:
@@ -92,10 +100,10 @@ class _FusedA2C(object):
         if self._moved():
             raise RuntimeError(f'an agent was moved after the {type(self).__name__} was built: its parameters left the '
                                f'buffer')
-        key = (N, T, E)
+        key = (N, T, E) if league is None else (N, T, E, 'league')
         ws = self._workspace.get(key)
         if ws is None:
-            nbytes = self._workspace_bytes(N, T, E)
+            nbytes = self._workspace_bytes(N, T, E) if league is None else self._league_workspace_bytes(N, T, E)
             ws = self._workspace[key] = (torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes)
         return (state.contiguous(), obs.contiguous(), actions.contiguous(), rewards.contiguous(), dones.contiguous(),
                 ws, N, T)
@@ -103,11 +111,13 @@ class _FusedA2C(object):
     def _check_envs(self, N):
         pass
 
-    def _outputs(self, N, T):
+    def _outputs(self, N, T, league=None):
         dev = self.params.device
+        # (a league writes only the columns of the members that learn: the rest stay zeros)
+        new = torch.empty if league is None else torch.zeros
         return (torch.empty_like(self.params), torch.empty(self._losses_shape, dtype=torch.float32, device=dev),
-                torch.empty((T, N), dtype=torch.float32, device=dev),
-                torch.empty((T, N), dtype=torch.float32, device=dev) if self.use_gae else None)
+                new((T, N), dtype=torch.float32, device=dev),
+                new((T, N), dtype=torch.float32, device=dev) if self.use_gae else None)
 
     def _losses(self, losses, values, returns):
         i = self._LOSS_INDEX
@@ -116,16 +126,19 @@ class _FusedA2C(object):
             res['returns'] = returns
         return res
 
-    def _grad_args(self, x0, obs, actions, rewards, dones, grad, losses, values, ws, nbytes, N, T):
+    def _grad_args(self, x0, obs, actions, rewards, dones, grad, losses, values, ws, nbytes, N, T, league=None):
         """the arguments `grad` and `update` share, up to num_inputs / num_members"""
         ptr = _lib.ptr
         return (ptr(self.params), ptr(x0), ptr(obs), ptr(actions), ptr(rewards), ptr(dones), *self._loss_args(),
-                self.value_loss, ptr(grad), ptr(losses), ptr(values), ptr(ws), nbytes, N, T, self.num_inputs,
+                *(ptr(t) for t in league or ()), self.value_loss, ptr(grad), ptr(losses), ptr(values), ptr(ws), nbytes, N, T, self.num_inputs,
                 *self._members)
 
-    def _adam_args(self, norm, apply=False):
+    def _adam_args(self, norm, apply=False, league=None):
         """the optimiser state and what follows it, up to max_grad_norm"""
-        return (_lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(norm), *self._step_args(apply), self.betas[0],
+        step = self._step_args(apply)
+        if apply and league is not None:  # (the league's apply: who steps is in offsets and learn)
+            step = (step[0], _lib.ptr(league[1]), _lib.ptr(league[2]), step[1])
+        return (_lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(norm), *step, self.betas[0],
                 self.betas[1], self.eps, self.max_grad_norm)
 
     # ------------------------------------------------------------------ the calls
@@ -136,12 +149,15 @@ class _FusedA2C(object):
         FusedA2CPopulation — plus `values`, (T, N): the value of every policy input, and with GAE `returns`, (T, N).
         state: the observation the rollout started from, (N, ...); out: what `policy_rollout` returned (or any dict
         with `observations` (T, N, ...), `actions`, `rewards`, `dones` (T, N))."""
-        x0, obs, actions, rewards, dones, (ws, nbytes), N, T = self._inputs(state, out)
-        grad, losses, values, returns = self._outputs(N, T)
+        return self._grad(state, out)
+
+    def _grad(self, state, out, league=None):
+        x0, obs, actions, rewards, dones, (ws, nbytes), N, T = self._inputs(state, out, league)
+        grad, losses, values, returns = self._outputs(N, T, league)
         dev = self.params.device
-        fn = getattr(_lib.lib(), self._ENTRY + ('grad_gae' if self.use_gae else 'grad'))
+        fn = getattr(_lib.lib(), self._entry(league) + ('grad_gae' if self.use_gae else 'grad'))
         rc = _lib.call(dev.index, fn, *self._grad_args(x0, obs, actions, rewards, dones, grad, losses, values, ws, nbytes,
-                                                       N, T),
+                                                       N, T, league),
                        _lib.stream_ptr(dev.index), *self._gae_args(returns))
         _lib.check(rc, f'{type(self).__name__}.grad')
         return grad, self._losses(losses, values, returns)
@@ -149,6 +165,9 @@ class _FusedA2C(object):
     def apply(self, grad: torch.Tensor) -> torch.Tensor:
         """clip_grad_norm_ + one Adam step of every agent on a gradient of the shape of `params` (not modified); returns
         its norm (device tensor: 0-dim for FusedA2CLearner, (P,) for FusedA2CPopulation)."""
+        return self._apply(grad)
+
+    def _apply(self, grad, league=None):
         dev = self.params.device
         if dev.type != 'cuda':
             raise _lib.WurmHipError(f'{type(self).__name__}.apply runs on the GPU')
@@ -156,9 +175,10 @@ class _FusedA2C(object):
             raise RuntimeError(f'grad must be a contiguous fp32 device tensor that matches params '
                                f'{tuple(self.params.shape)}')
         norm = torch.empty(self._norm_shape, dtype=torch.float32, device=dev)
-        args = self._adam_args(norm, apply=True)
-        rc = _lib.call(dev.index, getattr(_lib.lib(), self._ENTRY + 'apply'), _lib.ptr(self.params), _lib.ptr(grad),
-                       *args, self.params.shape[-1], *self._members, _lib.stream_ptr(dev.index))
+        args = self._adam_args(norm, apply=True, league=league)
+        rows = () if league is None else (league[0].numel(),)
+        rc = _lib.call(dev.index, getattr(_lib.lib(), self._entry(league) + 'apply'), _lib.ptr(self.params),
+                       _lib.ptr(grad), *args, self.params.shape[-1], *rows, *self._members, _lib.stream_ptr(dev.index))
         _lib.check(rc, f'{type(self).__name__}.apply')
         self.step += 1
         return self._per_agent(norm)
@@ -166,13 +186,16 @@ class _FusedA2C(object):
     def update(self, state: torch.Tensor, out: dict) -> dict:
         """One optimiser step of every agent from one rollout window, in three launches: the losses of `grad` plus
         `grad_norm` (before clipping) and `grad` (unclipped), all device tensors — nothing is copied to the host."""
-        x0, obs, actions, rewards, dones, (ws, nbytes), N, T = self._inputs(state, out)
-        grad, losses, values, returns = self._outputs(N, T)
+        return self._update(state, out)
+
+    def _update(self, state, out, league=None):
+        x0, obs, actions, rewards, dones, (ws, nbytes), N, T = self._inputs(state, out, league)
+        grad, losses, values, returns = self._outputs(N, T, league)
         dev = self.params.device
         norm = torch.empty(self._norm_shape, dtype=torch.float32, device=dev)
-        fn = getattr(_lib.lib(), self._ENTRY + ('update_gae' if self.use_gae else 'update'))
+        fn = getattr(_lib.lib(), self._entry(league) + ('update_gae' if self.use_gae else 'update'))
         rc = _lib.call(dev.index, fn, *self._grad_args(x0, obs, actions, rewards, dones, grad, losses, values, ws, nbytes,
-                                                       N, T),
+                                                       N, T, league),
                        *self._adam_args(norm), _lib.stream_ptr(dev.index), *self._gae_args(returns))
         _lib.check(rc, f'{type(self).__name__}.update')
         self.step += 1

@@ -86,6 +86,81 @@ class FusedA2CPopulation(_FusedA2C):
         if N % self.num_members != 0:
             raise RuntimeError(f'{N} envs do not divide into {self.num_members} members')
 
+    # ------------------------------------------------------------------ learning from a league window
+
+    def _league(self, plan, learn, what):
+        """None without a plan, else the checked (order, offsets, learn) the league entry points take; `learn` as bytes"""
+        name = f'{type(self).__name__}.{what}'
+        if plan is None:
+            if learn is not None:
+                raise RuntimeError(f'{name}: learn goes with a plan (without one every member learns)')
+            return None
+        from wurm_amd.envs._multi_league import LeaguePlan
+        if not isinstance(plan, LeaguePlan):
+            raise RuntimeError(f'{name}: plan must come from league_plan, got {type(plan).__name__}')
+        P, dev = self.num_members, self.params.device
+        if plan.num_policies != P:
+            raise RuntimeError(f'{name}: the plan names {plan.num_policies} policies but the population has {P} members')
+        if learn is not None:
+            if not isinstance(learn, torch.Tensor) or tuple(learn.shape) != (P,) or \
+                    learn.dtype not in (torch.bool, torch.uint8):
+                got = f'{tuple(learn.shape)} {learn.dtype}' if isinstance(learn, torch.Tensor) else type(learn).__name__
+                raise RuntimeError(f'{name}: learn must be a ({P},) bool or uint8 tensor, got {got}')
+        if dev.type != 'cuda':
+            raise _lib.WurmHipError(f'{name} runs on the GPU: move the agents to the device first')
+        if plan.order.device != dev:
+            raise RuntimeError(f'{name}: the plan is on {plan.order.device}, the agents on {dev}')
+        if learn is not None:
+            if learn.device != dev:
+                raise RuntimeError(f'{name}: learn is on {learn.device}, the agents on {dev}')
+            learn = learn.contiguous().view(torch.uint8)
+        return plan.order, plan.offsets, learn
+
+    @staticmethod
+    def _check_league(N, league):
+        if league[0].numel() != N:
+            raise RuntimeError(f'the window has {N} columns, the plan {league[0].numel()} rows (num_snakes x num_envs)')
+
+    def _league_workspace_bytes(self, N, T, E):
+        return _lib.lib().wurm_a2c_ff_league_workspace_bytes(N, T, E, self.num_members)
+
+    def grad(self, state: torch.Tensor, out: dict, plan=None, learn=None):
+        """FusedA2CLearner.grad for every member.  With `plan`, a `LeaguePlan` of `num_members` policies (MultiSnake.
+        league_plan), the window is a league's: `out` what `league_window` returned, (T, K N, ...) tensors whose column
+        k N + i is snake k of env i, and `state` the observations it started from, the dict of K (N, ...) tensors that
+        `reset`, `step` and the window's 'state' are, or a (K, N, ...) tensor.  Member
+        a learns from the columns the plan gives policy a, however many (include/wurm_hip.h: wurm_a2c_ff_league_*): its
+        results are bit for bit those of a FusedA2CLearner on copies of these columns in the plan's order.
+        learn: (P,) bool / uint8 device tensor or None; a member with learn[a] == 0, like one without columns, gets
+        zeros for its `grad`, losses and `grad_norm`, and `update` / `apply` leave its weights and Adam state alone.
+        `values` / `returns` are (T, K N), zeros in the columns of such members."""
+        return self._grad(self._rows(state, plan), out, self._league(plan, learn, 'grad'))
+
+    def update(self, state: torch.Tensor, out: dict, plan=None, learn=None) -> dict:
+        """FusedA2CLearner.update for every member, in three launches; `plan` and `learn` as for `grad`.  `step` is
+        shared: it advances for every member, also for one that sits this window out, whose next Adam step then has the
+        bias corrections of the shared count."""
+        return self._update(self._rows(state, plan), out, self._league(plan, learn, 'update'))
+
+    def apply(self, grad: torch.Tensor, plan=None, learn=None) -> torch.Tensor:
+        """FusedA2CLearner.apply for every member; with `plan` (and `learn`) only the members that `grad` let learn step"""
+        return self._apply(grad, self._league(plan, learn, 'apply'))
+
+    @staticmethod
+    def _rows(state, plan):
+        """the observations a league window started from as ONE tensor whose rows are the columns k N + i: a (K, N, ...)
+        tensor as it is; the dict `reset` / `step` / `league_window` return (agent_0 .. agent_{K-1}, (N, ...) each) in
+        place when its tensors are consecutive views of one buffer (they are), else stacked once"""
+        if plan is None or not isinstance(state, dict):
+            return state
+        vals = list(state.values())
+        v0, rest = vals[0], vals[0][0].numel() if len(vals[0]) else 0
+        step = 4 * v0.shape[0] * rest
+        if all(v.is_contiguous() and v.dtype == torch.float32 and v.shape == v0.shape and
+               v.data_ptr() == v0.data_ptr() + j * step for j, v in enumerate(vals)):
+            return v0.as_strided((len(vals) * v0.shape[0], rest), (rest, 1))
+        return torch.stack([v.reshape(v.shape[0], -1) for v in vals])
+
     def _moved(self):
         return any(_parts(a)[0].data_ptr() != row.data_ptr() for a, row in zip(self.agents, self.params))
 

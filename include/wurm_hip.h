@@ -683,7 +683,11 @@ int wurm_single_stats(const float *envs, const float *reward, const uint8_t *don
  *   actions (T,N) int64 in 0..3;  rewards (T,N) fp32;  dones (T,N) bytes.
  *   loss = mean l(v - R) - mean((R - v) log p~[a]) - entropy_coef * mean H, l = value_loss_kind, log p~ =
  *   log(clamp(p, eps32, 1 - eps32)), H = - sum_k p_k log p~_k, means over the N T samples, R and R - v constants.
- *   num_inputs: 3 (2n+1)^2 for n <= 6 ('partial_n') or 4 ('positions'); anything else is WURM_ERR_UNSUPPORTED. */
+ *   num_inputs: 3 (2n+1)^2 for n <= 6 ('partial_n') or 4 ('positions'); anything else is WURM_ERR_UNSUPPORTED.
+ * The PARAMETER NAMES of the wurm_a2c_ff_* prototypes (this section and the next two) are read by the Python loader:
+ * wurm_amd/_lib.py keeps them (`fn.argnames`) and the learners place their arguments by them (`_lib.call_named`), so
+ * these prototypes are the one statement of the argument order.  The same value has the same name in every prototype;
+ * renaming a parameter here renames what the callers must supply. */
 #define WURM_A2C_SMOOTH_L1 0 /* F.smooth_l1_loss, beta = 1 */
 #define WURM_A2C_MSE 1       /* (v - R)^2 */
 

@@ -1,6 +1,6 @@
 """`FusedA2CPopulation.grad / update / apply(..., plan=, learn=)`: a population that learns from a league window, member a
 from the columns the line-up gives policy a, however many (include/wurm_hip.h: wurm_a2c_ff_league_*; kernels:
-a2c_ff_main_kernel<GAE, false, true> and a2c_ff_*_league_kernel of wurm_amd/csrc/a2c_learner.hpp).
+a2c_ff_main_kernel<GAE, Kind::League> and a2c_ff_*_league_kernel of wurm_amd/csrc/a2c_learner.hpp).
 
 The expected values come from code the league form does not touch: a fresh `FusedA2CLearner` per policy, loaded with that
 member's row of the weights, its Adam state and the shared `step`, and updated on `index_select`ed contiguous copies of

@@ -5,6 +5,7 @@ product raises.  The CPU oracle under oracle/ is test infrastructure and is neve
 """
 import contextlib
 import ctypes
+import operator
 import os
 import subprocess
 
@@ -186,6 +187,9 @@ def _declare_prototypes(l):
         if args == ['void']:
             args = []
         fn.argtypes = [ctypes.c_void_p if '*' in a else _CTYPES[a.replace('const ', '').split()[0]] for a in args]
+        names = fn.argnames = tuple(re.search(r'\w+$', a).group() for a in args)
+        # call_named picks the arguments by them: one C call per entry point (itemgetter wants two names or more)
+        fn.pick = operator.itemgetter(*names) if len(names) > 1 else lambda values, names=names: [values[n] for n in names]
     missing = [n for n in SYMBOLS if n not in declared]
     if missing:  # a symbol without argtypes would get ctypes' default int conversion for 64-bit arguments
         raise WurmHipError(f'{header}: no prototype found for {missing}')
@@ -418,6 +422,18 @@ def call(device_index, fn, *args):
         with torch.cuda.device(device_index):
             return fn(*args)
     return fn(*args)
+
+
+def call_named(device_index, fn, values: dict):
+    """`call` with the arguments picked out of `values` by the parameter names of fn's prototype in include/wurm_hip.h, in
+    the header's order: the header alone says where an argument goes.  `values` may hold more names than fn takes; a
+    declared name that it lacks is a TypeError.  device_index None: an entry point that launches nothing, called as it
+    is (no device needed)."""
+    try:
+        args = fn.pick(values)
+    except KeyError as e:
+        raise TypeError(f'{fn.__name__}: no value for its parameter {e.args[0]!r}') from None
+    return fn(*args) if device_index is None else call(device_index, fn, *args)
 
 
 def u64(x):

@@ -3,8 +3,8 @@
 //                         every workgroup writes ITS gradient (P floats) and loss sums to the caller's workspace
 //   a2c_ff_reduce_kernel  sums the workgroups' partials in workgroup order into grad / losses
 //   a2c_ff_apply_kernel   ||g|| in a fixed order (every workgroup computes the same bits), clip, Adam
-// and the three with a member dimension in the grid (a2c_ff_main_kernel<GAE, true>, a2c_ff_*_pop_kernel): P updates at once
-// and with an index list of columns per member (a2c_ff_main_kernel<GAE, false, true>, a2c_ff_*_league_kernel): a league
+// and the three with a member dimension in the grid (a2c_ff_main_kernel<GAE, Kind::Pop>, a2c_ff_*_pop_kernel): P updates at once
+// and with an index list of columns per member (a2c_ff_main_kernel<GAE, Kind::League>, a2c_ff_*_league_kernel): a league
 // No float atomics anywhere: two runs on the same inputs give the same bits.
 //
 // Main kernel.  A workgroup (256 threads) owns the envs [wg N / G, (wg + 1) N / G) with all T + 1 rows of each (the T
@@ -132,9 +132,12 @@ __device__ __forceinline__ LeagueMember league_member(const long long *__restric
     return m;
 }
 
-template <bool GAE, bool POP, bool LEAGUE = false> struct kernel_args { using type = typename main_args<GAE>::type; };
-template <bool GAE> struct kernel_args<GAE, true, false> { using type = PopArgs<typename main_args<GAE>::type>; };
-template <bool GAE> struct kernel_args<GAE, false, true> { using type = LeagueArgs<typename main_args<GAE>::type>; };
+// the three kinds of update: one agent, a population (PopArgs), a league (LeagueArgs)
+enum class Kind { Alone, Pop, League };
+
+template <bool GAE, Kind K> struct kernel_args { using type = typename main_args<GAE>::type; };
+template <bool GAE> struct kernel_args<GAE, Kind::Pop> { using type = PopArgs<typename main_args<GAE>::type>; };
+template <bool GAE> struct kernel_args<GAE, Kind::League> { using type = LeagueArgs<typename main_args<GAE>::type>; };
 
 // acc[i][j] += sum_k A[4 tr + i][k] * B[tj + 16 j][k], k < K (a multiple of 4)
 __device__ __forceinline__ void gemm_nt(const float *A, const float *B, int K, int tr, int tj, float (&acc)[4][4])
@@ -193,9 +196,10 @@ __device__ __forceinline__ float value_loss_derivative(int loss_kind, float dl)
     return 2.0f * dl; // squared error
 }
 
-template <bool GAE, bool POP = false, bool LEAGUE = false>
-__global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(typename kernel_args<GAE, POP, LEAGUE>::type g)
+template <bool GAE, Kind K = Kind::Alone>
+__global__ __launch_bounds__(THREADS) void a2c_ff_main_kernel(typename kernel_args<GAE, K>::type g)
 {
+    constexpr bool POP = K == Kind::Pop, LEAGUE = K == Kind::League;
     __shared__ __attribute__((aligned(16))) float Xs[TILE * LD], W1s[HID * LD], W2s[HID * LD], W2Ts[HID * LD];
     __shared__ __attribute__((aligned(16))) float H1s[TILE * LD], H2s[TILE * LD], dZ2s[TILE * LD], dZ1s[TILE * LD];
     __shared__ __attribute__((aligned(16))) float Wps[4 * HID], Wvs[HID], b1s[HID], b2s[HID], zs[TILE * 8];

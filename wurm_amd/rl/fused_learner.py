@@ -13,6 +13,8 @@ custom value loss are not part of the fused path (NotImplementedError: keep wurm
 normalised returns need the mean and the standard deviation of all N T returns between the scan and the backward pass,
 which one workgroup per block of envs cannot know.
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -28,14 +30,21 @@ def _parts(agent):
             agent.value_head.weight, agent.value_head.bias]
 
 
+# One of the three kinds of entry points, as a call sees it.  entry: the prefix of their names ('wurm_a2c_ff_', '..._pop_',
+# '..._league_');  check(N): raises unless the kind takes a window of N columns;  new: torch.empty, or torch.zeros where
+# the kernels leave columns of `values` / `returns` unwritten;  names: the values the kind adds under the header's
+# parameter names;  keep: tensors made for this call whose addresses are among them
+_Kind = collections.namedtuple('_Kind', 'entry check new names keep')
+_any_envs = lambda N: None
+
+
 class _FusedA2C(object):
     """What FusedA2CLearner and FusedA2CPopulation (fused_population.py) share: the constructor's refusals, the packing of
     the agents into one buffer, the checks of a rollout window, the output tensors and the marshalling of the three calls.
-    A subclass says which entry points it calls (`_ENTRY`), how its hyper-parameters are kept (`_own`) and cross the ABI
-    (`_loss_args`, `_step_args`, `_gae_args`), and what one agent's part of `losses` and `grad_norm` is.
-    `league` is None everywhere but in FusedA2CPopulation's calls with a plan: there it is the checked
-    (order, offsets, learn) of the line-up, and the calls go to the `wurm_a2c_ff_league_` entry points."""
-    _ENTRY = None       # 'wurm_a2c_ff_' or 'wurm_a2c_ff_pop_'
+    A subclass says how its hyper-parameters are kept (`_own`), what one agent's part of `losses` and `grad_norm` is, and,
+    at the top of `grad`, `apply` and `update`, which kind of entry points the call goes to (`_kind`: a `_Kind`).
+    Every call hands the library ONE dict of values under the parameter names of include/wurm_hip.h (`_lib.call_named`):
+    the header alone says in which order an entry point takes them."""
     _WHOSE = None       # 'agent' / 'agents', for the messages
     _LOSS_INDEX = None  # the three indices into `losses` that give value_loss, policy_loss and entropy
 
@@ -68,10 +77,19 @@ class _FusedA2C(object):
 
     # ------------------------------------------------------------------ plumbing
 
-    def _entry(self, league):
-        return self._ENTRY if league is None else 'wurm_a2c_ff_league_'
+    def _values(self, kind):
+        """what an entry point of `kind` may ask for by name, the window and the outputs aside"""
+        values = {'params': self.params.data_ptr(), 'exp_avg': self.exp_avg.data_ptr(),
+                  'exp_avg_sq': self.exp_avg_sq.data_ptr(), 'step': self.step + 1, 'beta1': self.betas[0],
+                  'beta2': self.betas[1], 'eps': self.eps, 'max_grad_norm': self.max_grad_norm,
+                  'num_params': self.params.shape[-1], 'value_loss_kind': self.value_loss, 'num_inputs': self.num_inputs,
+                  'stream': _lib.stream_ptr(self.params.device.index)}
+        values.update(kind.names)
+        return values
 
-    def _inputs(self, state, out, league=None):
+    def _window(self, kind, state, out):
+        """(values, tensors): the checked rollout window, fresh outputs and the workspace on top of `_values`, and the
+        tensors behind the addresses among them, by parameter name"""
         dev, E = self.params.device, self.num_inputs
         if dev.type != 'cuda':
             raise _lib.WurmHipError(f'{type(self).__name__}.grad / update run on the GPU: move the {self._WHOSE} to the '
@@ -80,10 +98,7 @@ class _FusedA2C(object):
         if rewards.dim() != 2 or rewards.numel() == 0:
             raise RuntimeError('rewards must be a non-empty (num_steps, num_envs) tensor')
         T, N = rewards.shape
-        if league is None:
-            self._check_envs(N)
-        else:
-            self._check_league(N, league)
+        kind.check(N)
         for name, t in (('state', state), ('observations', obs), ('actions', actions), ('rewards', rewards),
                         ('dones', dones)):
             if t.device != dev:
@@ -100,46 +115,35 @@ class _FusedA2C(object):
         if self._moved():
             raise RuntimeError(f'an agent was moved after the {type(self).__name__} was built: its parameters left the '
                                f'buffer')
-        key = (N, T, E) if league is None else (N, T, E, 'league')
-        ws = self._workspace.get(key)
+        values = self._values(kind)
+        values['num_envs'], values['num_steps'] = N, T
+        ws = self._workspace.get((kind.entry, N, T, E))
         if ws is None:
-            nbytes = self._workspace_bytes(N, T, E) if league is None else self._league_workspace_bytes(N, T, E)
-            ws = self._workspace[key] = (torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes)
-        return (state.contiguous(), obs.contiguous(), actions.contiguous(), rewards.contiguous(), dones.contiguous(),
-                ws, N, T)
+            nbytes = _lib.call_named(None, getattr(_lib.lib(), kind.entry + 'workspace_bytes'), values)
+            ws = self._workspace[kind.entry, N, T, E] = (torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes)
+        new, f32 = kind.new, torch.float32
+        tensors = {'obs0': state.contiguous(), 'obs': obs.contiguous(), 'actions': actions.contiguous(),
+                   'rewards': rewards.contiguous(), 'dones': dones.contiguous(), 'workspace': ws[0],
+                   'grad': torch.empty_like(self.params),
+                   'losses': torch.empty(self._losses_shape, dtype=f32, device=dev),
+                   'values_out': new((T, N), dtype=f32, device=dev),
+                   'returns_out': new((T, N), dtype=f32, device=dev) if self.use_gae else None}
+        values.update({name: _lib.ptr(t) for name, t in tensors.items()}, workspace_bytes=ws[1])
+        return values, tensors
 
-    def _check_envs(self, N):
-        pass
+    def _call(self, kind, what, values):
+        """the entry point `what` ('grad', 'apply', 'update') of `kind`, or its GAE form"""
+        gae = '_gae' if self.use_gae and what != 'apply' else ''
+        fn = getattr(_lib.lib(), kind.entry + what + gae)
+        _lib.check(_lib.call_named(self.params.device.index, fn, values), f'{type(self).__name__}.{what}')
 
-    def _outputs(self, N, T, league=None):
-        dev = self.params.device
-        # (a league writes only the columns of the members that learn: the rest stay zeros)
-        new = torch.empty if league is None else torch.zeros
-        return (torch.empty_like(self.params), torch.empty(self._losses_shape, dtype=torch.float32, device=dev),
-                new((T, N), dtype=torch.float32, device=dev),
-                new((T, N), dtype=torch.float32, device=dev) if self.use_gae else None)
-
-    def _losses(self, losses, values, returns):
-        i = self._LOSS_INDEX
-        res = {'value_loss': losses[i[0]], 'policy_loss': losses[i[1]], 'entropy': losses[i[2]], 'values': values}
-        if returns is not None:
-            res['returns'] = returns
+    def _losses(self, tensors):
+        i, losses = self._LOSS_INDEX, tensors['losses']
+        res = {'value_loss': losses[i[0]], 'policy_loss': losses[i[1]], 'entropy': losses[i[2]],
+               'values': tensors['values_out']}
+        if tensors['returns_out'] is not None:
+            res['returns'] = tensors['returns_out']
         return res
-
-    def _grad_args(self, x0, obs, actions, rewards, dones, grad, losses, values, ws, nbytes, N, T, league=None):
-        """the arguments `grad` and `update` share, up to num_inputs / num_members"""
-        ptr = _lib.ptr
-        return (ptr(self.params), ptr(x0), ptr(obs), ptr(actions), ptr(rewards), ptr(dones), *self._loss_args(),
-                *(ptr(t) for t in league or ()), self.value_loss, ptr(grad), ptr(losses), ptr(values), ptr(ws), nbytes, N, T, self.num_inputs,
-                *self._members)
-
-    def _adam_args(self, norm, apply=False, league=None):
-        """the optimiser state and what follows it, up to max_grad_norm"""
-        step = self._step_args(apply)
-        if apply and league is not None:  # (the league's apply: who steps is in offsets and learn)
-            step = (step[0], _lib.ptr(league[1]), _lib.ptr(league[2]), step[1])
-        return (_lib.ptr(self.exp_avg), _lib.ptr(self.exp_avg_sq), _lib.ptr(norm), *step, self.betas[0],
-                self.betas[1], self.eps, self.max_grad_norm)
 
     # ------------------------------------------------------------------ the calls
 
@@ -149,25 +153,19 @@ class _FusedA2C(object):
         FusedA2CPopulation — plus `values`, (T, N): the value of every policy input, and with GAE `returns`, (T, N).
         state: the observation the rollout started from, (N, ...); out: what `policy_rollout` returned (or any dict
         with `observations` (T, N, ...), `actions`, `rewards`, `dones` (T, N))."""
-        return self._grad(state, out)
+        return self._grad(self._kind(), state, out)
 
-    def _grad(self, state, out, league=None):
-        x0, obs, actions, rewards, dones, (ws, nbytes), N, T = self._inputs(state, out, league)
-        grad, losses, values, returns = self._outputs(N, T, league)
-        dev = self.params.device
-        fn = getattr(_lib.lib(), self._entry(league) + ('grad_gae' if self.use_gae else 'grad'))
-        rc = _lib.call(dev.index, fn, *self._grad_args(x0, obs, actions, rewards, dones, grad, losses, values, ws, nbytes,
-                                                       N, T, league),
-                       _lib.stream_ptr(dev.index), *self._gae_args(returns))
-        _lib.check(rc, f'{type(self).__name__}.grad')
-        return grad, self._losses(losses, values, returns)
+    def _grad(self, kind, state, out):
+        values, tensors = self._window(kind, state, out)
+        self._call(kind, 'grad', values)
+        return tensors['grad'], self._losses(tensors)
 
     def apply(self, grad: torch.Tensor) -> torch.Tensor:
         """clip_grad_norm_ + one Adam step of every agent on a gradient of the shape of `params` (not modified); returns
         its norm (device tensor: 0-dim for FusedA2CLearner, (P,) for FusedA2CPopulation)."""
-        return self._apply(grad)
+        return self._apply(self._kind(), grad)
 
-    def _apply(self, grad, league=None):
+    def _apply(self, kind, grad):
         dev = self.params.device
         if dev.type != 'cuda':
             raise _lib.WurmHipError(f'{type(self).__name__}.apply runs on the GPU')
@@ -175,33 +173,26 @@ class _FusedA2C(object):
             raise RuntimeError(f'grad must be a contiguous fp32 device tensor that matches params '
                                f'{tuple(self.params.shape)}')
         norm = torch.empty(self._norm_shape, dtype=torch.float32, device=dev)
-        args = self._adam_args(norm, apply=True, league=league)
-        rows = () if league is None else (league[0].numel(),)
-        rc = _lib.call(dev.index, getattr(_lib.lib(), self._entry(league) + 'apply'), _lib.ptr(self.params),
-                       _lib.ptr(grad), *args, self.params.shape[-1], *rows, *self._members, _lib.stream_ptr(dev.index))
-        _lib.check(rc, f'{type(self).__name__}.apply')
+        values = self._values(kind)
+        values['grad'], values['grad_norm'] = grad.data_ptr(), norm.data_ptr()
+        self._call(kind, 'apply', values)
         self.step += 1
         return self._per_agent(norm)
 
     def update(self, state: torch.Tensor, out: dict) -> dict:
         """One optimiser step of every agent from one rollout window, in three launches: the losses of `grad` plus
         `grad_norm` (before clipping) and `grad` (unclipped), all device tensors — nothing is copied to the host."""
-        return self._update(state, out)
+        return self._update(self._kind(), state, out)
 
-    def _update(self, state, out, league=None):
-        x0, obs, actions, rewards, dones, (ws, nbytes), N, T = self._inputs(state, out, league)
-        grad, losses, values, returns = self._outputs(N, T, league)
-        dev = self.params.device
-        norm = torch.empty(self._norm_shape, dtype=torch.float32, device=dev)
-        fn = getattr(_lib.lib(), self._entry(league) + ('update_gae' if self.use_gae else 'update'))
-        rc = _lib.call(dev.index, fn, *self._grad_args(x0, obs, actions, rewards, dones, grad, losses, values, ws, nbytes,
-                                                       N, T, league),
-                       *self._adam_args(norm), _lib.stream_ptr(dev.index), *self._gae_args(returns))
-        _lib.check(rc, f'{type(self).__name__}.update')
+    def _update(self, kind, state, out):
+        values, tensors = self._window(kind, state, out)
+        norm = torch.empty(self._norm_shape, dtype=torch.float32, device=self.params.device)
+        values['grad_norm'] = norm.data_ptr()
+        self._call(kind, 'update', values)
         self.step += 1
-        res = self._losses(losses, values, returns)
+        res = self._losses(tensors)
         res['grad_norm'] = self._per_agent(norm)
-        res['grad'] = grad
+        res['grad'] = tensors['grad']
         return res
 
     # ------------------------------------------------------------------ checkpoints
@@ -244,8 +235,7 @@ class FusedA2CLearner(_FusedA2C):
         value_loss: 'smooth_l1' (F.smooth_l1_loss, the reference's default) or 'mse'
         use_gae, gae_lambda: A2C's; `gae_lambda` is required with `use_gae` and ignored without it
     """
-    _ENTRY, _WHOSE, _LOSS_INDEX = 'wurm_a2c_ff_', 'agent', (0, 1, 2)
-    _members, _losses_shape, _norm_shape = (), (3,), (1,)
+    _WHOSE, _LOSS_INDEX, _losses_shape, _norm_shape = 'agent', (0, 1, 2), (3,), (1,)
 
     def __init__(self, agent: FeedforwardAgent, lr: float = 1e-3, gamma: float = 0.99, entropy_coef: float = 0.0,
                  max_grad_norm: float = 0.5, betas=(0.9, 0.999), eps: float = 1e-8, value_loss: str = 'smooth_l1',
@@ -268,10 +258,6 @@ class FusedA2CLearner(_FusedA2C):
     def _moved(self):
         return _parts(self.agent)[0].data_ptr() != self.params.data_ptr()
 
-    @staticmethod
-    def _workspace_bytes(N, T, E):
-        return _lib.lib().wurm_a2c_ff_workspace_bytes(N, T, E)
-
     def _fits(self, grad):
         return grad.numel() == self.params.numel()
 
@@ -279,12 +265,7 @@ class FusedA2CLearner(_FusedA2C):
     def _per_agent(norm):
         return norm[0]
 
-    # the stand-alone entry points take the hyper-parameters by value
-    def _loss_args(self):
-        return self.gamma, self.entropy_coef
-
-    def _step_args(self, apply):
-        return self.step + 1, self.lr
-
-    def _gae_args(self, returns):
-        return (self.gamma_lambda, _lib.ptr(returns)) if self.use_gae else ()
+    def _kind(self):
+        # the stand-alone entry points take any number of envs, and the hyper-parameters by value as they are at this call
+        return _Kind('wurm_a2c_ff_', _any_envs, torch.empty, {'gamma': self.gamma, 'entropy_coef': self.entropy_coef,
+                                                              'lr': self.lr, 'gamma_lambda': self.gamma_lambda}, None)

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from wurm_amd import _lib
-from wurm_amd.rl.fused_learner import _FusedA2C, _parts
+from wurm_amd.rl.fused_learner import _FusedA2C, _Kind, _parts
 
 
 def _per_member(name, value, P):
@@ -47,7 +47,7 @@ class FusedA2CPopulation(_FusedA2C):
     (P, num_params), the losses and `grad_norm` (P,); state and out are what a `policy_rollout(..., population=P)` started
     from and returned, (N, ...) and (T, N, ...).
     """
-    _ENTRY, _WHOSE, _LOSS_INDEX = 'wurm_a2c_ff_pop_', 'agents', tuple((slice(None), i) for i in range(3))
+    _WHOSE, _LOSS_INDEX = 'agents', tuple((slice(None), i) for i in range(3))
     _STATE_TENSORS, _STATE_NUMBERS = _FusedA2C._STATE_TENSORS + ('hyper',), _FusedA2C._STATE_NUMBERS + ('generation',)
 
     def __init__(self, agents, lr=1e-3, gamma=0.99, entropy_coef=0.0, max_grad_norm: float = 0.5, betas=(0.9, 0.999),
@@ -59,16 +59,15 @@ class FusedA2CPopulation(_FusedA2C):
         super().__init__(agents, lr, gamma, entropy_coef, max_grad_norm, betas, eps, value_loss, use_gae, gae_lambda)
         self.agents = agents
         self.num_members = P
-        self._members, self._losses_shape, self._norm_shape = (P,), (P, 3), (P,)
+        self._losses_shape, self._norm_shape = (P, 3), (P,)
         # gamma * lambda is one Python float per member, rounded once (FusedA2CLearner.gamma_lambda)
         self.gamma_lambda = [float(np.float32(g * l)) for g, l in zip(self.gamma, self.gae_lambda)] if use_gae else None
         # the hyper-parameter table (P, 4) of doubles: filled by the library on the host, copied to the device ONCE
         f32 = lambda values: (ctypes.c_float * P)(*values)
         table = np.zeros((P, 4), dtype=np.float64)
-        columns = [f32(self.lr), f32(self.gamma), f32(self.entropy_coef), f32(self.gamma_lambda) if use_gae else None]
-        rc = _lib.lib().wurm_a2c_ff_pop_hyper(*[ctypes.addressof(c) if c is not None else None for c in columns],
-                                              _lib.i64(P), table.ctypes.data)
-        _lib.check(rc, 'FusedA2CPopulation: lr / gae_lambda')
+        values = {'lr': f32(self.lr), 'gamma': f32(self.gamma), 'entropy_coef': f32(self.entropy_coef),
+                  'gamma_lambda': f32(self.gamma_lambda) if use_gae else None, 'num_members': P, 'table': table.ctypes.data}
+        _lib.check(_lib.call_named(None, _lib.lib().wurm_a2c_ff_pop_hyper, values), 'FusedA2CPopulation: lr / gae_lambda')
         self.hyper = torch.from_numpy(table).to(self.params.device)
         self.generation = 0  # the number of `exploit` calls so far: the counter of their random draws
 
@@ -88,13 +87,15 @@ class FusedA2CPopulation(_FusedA2C):
 
     # ------------------------------------------------------------------ learning from a league window
 
-    def _league(self, plan, learn, what):
-        """None without a plan, else the checked (order, offsets, learn) the league entry points take; `learn` as bytes"""
+    def _kind(self, plan, learn, what):
+        """The kind of a call: the population's without a plan, else the league's with the checked plan and `learn` (as
+        bytes).  Both read a member's lr, gamma, entropy_coef and gamma_lambda from its row of the table."""
         name = f'{type(self).__name__}.{what}'
+        names = {'hyper': self.hyper.data_ptr(), 'num_members': self.num_members}
         if plan is None:
             if learn is not None:
                 raise RuntimeError(f'{name}: learn goes with a plan (without one every member learns)')
-            return None
+            return _Kind('wurm_a2c_ff_pop_', self._check_envs, torch.empty, names, None)
         from wurm_amd.envs._multi_league import LeaguePlan
         if not isinstance(plan, LeaguePlan):
             raise RuntimeError(f'{name}: plan must come from league_plan, got {type(plan).__name__}')
@@ -114,15 +115,14 @@ class FusedA2CPopulation(_FusedA2C):
             if learn.device != dev:
                 raise RuntimeError(f'{name}: learn is on {learn.device}, the agents on {dev}')
             learn = learn.contiguous().view(torch.uint8)
-        return plan.order, plan.offsets, learn
+        rows = plan.order.numel()
+        names.update(order=plan.order.data_ptr(), offsets=plan.offsets.data_ptr(), learn=_lib.ptr(learn), num_rows=rows)
 
-    @staticmethod
-    def _check_league(N, league):
-        if league[0].numel() != N:
-            raise RuntimeError(f'the window has {N} columns, the plan {league[0].numel()} rows (num_snakes x num_envs)')
-
-    def _league_workspace_bytes(self, N, T, E):
-        return _lib.lib().wurm_a2c_ff_league_workspace_bytes(N, T, E, self.num_members)
+        def check(N):
+            if rows != N:
+                raise RuntimeError(f'the window has {N} columns, the plan {rows} rows (num_snakes x num_envs)')
+        # (a league writes only the columns of the members that learn: the rest stay zeros)
+        return _Kind('wurm_a2c_ff_league_', check, torch.zeros, names, learn)
 
     def grad(self, state: torch.Tensor, out: dict, plan=None, learn=None):
         """FusedA2CLearner.grad for every member.  With `plan`, a `LeaguePlan` of `num_members` policies (MultiSnake.
@@ -134,17 +134,19 @@ class FusedA2CPopulation(_FusedA2C):
         learn: (P,) bool / uint8 device tensor or None; a member with learn[a] == 0, like one without columns, gets
         zeros for its `grad`, losses and `grad_norm`, and `update` / `apply` leave its weights and Adam state alone.
         `values` / `returns` are (T, K N), zeros in the columns of such members."""
-        return self._grad(self._rows(state, plan), out, self._league(plan, learn, 'grad'))
+        state = self._rows(state, plan)
+        return self._grad(self._kind(plan, learn, 'grad'), state, out)
 
     def update(self, state: torch.Tensor, out: dict, plan=None, learn=None) -> dict:
         """FusedA2CLearner.update for every member, in three launches; `plan` and `learn` as for `grad`.  `step` is
         shared: it advances for every member, also for one that sits this window out, whose next Adam step then has the
         bias corrections of the shared count."""
-        return self._update(self._rows(state, plan), out, self._league(plan, learn, 'update'))
+        state = self._rows(state, plan)
+        return self._update(self._kind(plan, learn, 'update'), state, out)
 
     def apply(self, grad: torch.Tensor, plan=None, learn=None) -> torch.Tensor:
         """FusedA2CLearner.apply for every member; with `plan` (and `learn`) only the members that `grad` let learn step"""
-        return self._apply(grad, self._league(plan, learn, 'apply'))
+        return self._apply(self._kind(plan, learn, 'apply'), grad)
 
     @staticmethod
     def _rows(state, plan):
@@ -164,25 +166,12 @@ class FusedA2CPopulation(_FusedA2C):
     def _moved(self):
         return any(_parts(a)[0].data_ptr() != row.data_ptr() for a, row in zip(self.agents, self.params))
 
-    def _workspace_bytes(self, N, T, E):
-        return _lib.lib().wurm_a2c_ff_pop_workspace_bytes(N, T, E, self.num_members)
-
     def _fits(self, grad):
         return grad.shape == self.params.shape
 
     @staticmethod
     def _per_agent(norm):
         return norm
-
-    # the population entry points read a member's lr, gamma, entropy_coef and gamma_lambda from its row of the table
-    def _loss_args(self):
-        return (_lib.ptr(self.hyper),)
-
-    def _step_args(self, apply):
-        return (_lib.ptr(self.hyper), self.step + 1) if apply else (self.step + 1,)
-
-    def _gae_args(self, returns):
-        return (_lib.ptr(returns),) if self.use_gae else ()
 
     # ------------------------------------------------------------------ population-based training
 

@@ -207,10 +207,12 @@ def to_device(fx, device):
 ENTRY_POINT_STEMS = ('grad', 'grad_gae', 'update', 'update_gae', 'apply')
 
 
-def run_entry_point(stem, given, device, E, T, N, members=0, lrs=(1e-3,)):
-    """One call of wurm_a2c_ff_<stem> (members == 0) or wurm_a2c_ff_pop_<stem> through ctypes, on inputs that depend on
-    the shape only, with the optional outputs values_out, grad_norm and returns_out handed over (`given`: filled with NaN
-    before, asserted written after) or null.  Returns every tensor the call writes whether they are given or not."""
+def build_entry_point(stem, given, device, E, T, N, members=0, lrs=(1e-3,)):
+    """What one call of wurm_a2c_ff_<stem> (members == 0) or wurm_a2c_ff_pop_<stem> through ctypes takes, on inputs that
+    depend on the shape only: (launch, t, window, optional) — `launch(stream)` makes the call with the arguments in the
+    entry point's order and returns its code, without synchronising; `t` the tensors it may write; `window` the rollout
+    window it reads (obs0, obs, rewards, actions, dones); `optional` the outputs values_out, returns_out and grad_norm
+    (`given`: filled with NaN; else None and handed over as null).  Every tensor stays alive as long as the result."""
     import ctypes
 
     import numpy as np
@@ -222,7 +224,6 @@ def run_entry_point(stem, given, device, E, T, N, members=0, lrs=(1e-3,)):
     t = {'params': (rnd(rows, P) - 0.5) * 0.5, 'grad': rnd(rows, P) - 0.5, 'exp_avg': (rnd(rows, P) - 0.5) * 1e-2,
          'exp_avg_sq': rnd(rows, P) * 1e-3, 'losses': torch.zeros(rows, 3)}
     t = {k: v.to(device) for k, v in t.items()}
-    before = {k: v.clone() for k, v in t.items()}
     obs0, obs, rewards = rnd(N, E).to(device), rnd(T, N, E).to(device), rnd(T, N).to(device)
     actions, dones = torch.randint(4, (T, N), generator=gen).to(device), (rnd(T, N) < 0.3).to(device)
     opt = lambda *shape: torch.full(shape, float('nan'), device=device) if given else None
@@ -241,7 +242,20 @@ def run_entry_point(stem, given, device, E, T, N, members=0, lrs=(1e-3,)):
         hyp, lr, mem, lam_tail = (0.99, 0.01), (lrs[0],), (), (float(np.float32(0.99 * 0.95)),)
     assert nbytes > 0
     ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    stream = _lib.stream_ptr(ws.device.index)
+    window = {'obs0': obs0, 'obs': obs, 'rewards': rewards, 'actions': actions, 'dones': dones}
+    optional = {'values_out': values, 'returns_out': returns, 'grad_norm': norm, 'workspace': ws, 'hyper': hyper if pop else None}
+
+    def launch(stream):
+        return _launch(lib, stem, pop, gae, P, t, window, optional, nbytes, N, T, E, hyp, lr, mem, lam_tail, stream)
+
+    return launch, t, window, optional
+
+
+def _launch(lib, stem, pop, gae, P, t, window, optional, nbytes, N, T, E, hyp, lr, mem, lam_tail, stream):
+    """the call of build_entry_point, arguments in the order of include/wurm_hip.h"""
+    ptr = lambda x: None if x is None else x.data_ptr()
+    obs0, obs, rewards, actions, dones = (window[k] for k in ('obs0', 'obs', 'rewards', 'actions', 'dones'))
+    values, returns, norm, ws = (optional[k] for k in ('values_out', 'returns_out', 'grad_norm', 'workspace'))
     head = (ptr(t['params']), ptr(obs0), ptr(obs), ptr(actions), ptr(rewards), ptr(dones), *hyp, 0, ptr(t['grad']),
             ptr(t['losses']), ptr(values), ptr(ws), nbytes, N, T, E, *mem)
     state = (ptr(t['exp_avg']), ptr(t['exp_avg_sq']), ptr(norm))
@@ -254,6 +268,19 @@ def run_entry_point(stem, given, device, E, T, N, members=0, lrs=(1e-3,)):
         rc = fn(*head, stream, *tail)
     else:
         rc = fn(*head, *state, *adam, stream, *tail)
+    return rc
+
+
+def run_entry_point(stem, given, device, E, T, N, members=0, lrs=(1e-3,)):
+    """One call of wurm_a2c_ff_<stem> (members == 0) or wurm_a2c_ff_pop_<stem> through ctypes (build_entry_point), with
+    the optional outputs values_out, grad_norm and returns_out handed over (`given`: filled with NaN before, asserted
+    written after) or null.  Returns every tensor the call writes whether they are given or not."""
+    from wurm_amd import _lib
+    launch, t, window, optional = build_entry_point(stem, given, device, E, T, N, members, lrs)
+    values, returns, norm = (optional[k] for k in ('values_out', 'returns_out', 'grad_norm'))
+    gae = stem.endswith('_gae')
+    before = {k: v.clone() for k, v in t.items()}
+    rc = launch(_lib.stream_ptr(torch.device(device).index))
     torch.cuda.synchronize()
     assert rc == _lib.OK
     written = ('grad', 'losses') if stem.startswith('grad') else ('params', 'exp_avg', 'exp_avg_sq') if stem == 'apply' \

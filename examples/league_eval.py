@@ -4,8 +4,9 @@ process per matchup.  Here every env of a MultiSnake batch gets a line-up of its
 policies, drawn at random, with or without replacement within an env — and all of them play at once:
 `MultiSnake.league_plan` sorts the (snake, env) rows by policy once, `MultiSnake.league_window` acts for every row with the
 policy its line-up names (one launch) and steps (one launch), and `wurm_amd.rl.LeagueTable` adds every policy's results on
-the device (one launch per window; copied to the host once, at the end).  `--save-video PATH` replays the first
-`--video-envs` envs of every `--video-interval`-th window after the fact (`record_start` / `record_frames`).
+the device (one launch per window; copied to the host once, at the end).  `--device-draw` draws and sorts the line-ups
+on the device (`MultiSnake.league_draw`: no host read, other line-ups than the host draw's).  `--save-video PATH` replays
+the first `--video-envs` envs of every `--video-interval`-th window after the fact (`record_start` / `record_frames`).
 
     python examples/league_eval.py --n-policies 16 --n-agents 4 --num-envs 512 --total-steps 200000
     python examples/league_eval.py --params population.pt --n-agents 2 --with-replacement
@@ -51,6 +52,7 @@ def main(argv=None):
     ap.add_argument('--window-steps', type=int, default=20)
     ap.add_argument('--total-steps', type=int, default=200000, help='env steps summed over the batch')
     ap.add_argument('--redraw', type=int, default=0, metavar='K', help='new line-ups every K windows (0: one draw)')
+    ap.add_argument('--device-draw', action='store_true', help='draw and sort the line-ups on the device (league_draw)')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--device', default='cuda')
     ap.add_argument('--observation', default='partial_5', help="'partial_n': the crop every agent sees")
@@ -74,12 +76,20 @@ def main(argv=None):
     video = WindowRecorder(env, args.save_video, range(min(args.video_envs, N)), args.video_interval) \
         if args.save_video else None
     g = torch.Generator().manual_seed(args.seed)
-    plan = env.league_plan(draw_lineup(A, K, N, args.with_replacement, g).to(env.device), A)
+
+    def draw():
+        if args.device_draw:
+            if not args.with_replacement and K > A:
+                raise SystemExit(f'{K} agents per env out of {A} policies needs --with-replacement')
+            return env.league_draw(A, replacement=args.with_replacement)
+        return env.league_plan(draw_lineup(A, K, N, args.with_replacement, g).to(env.device), A)
+
+    plan = draw()
     state = env.reset()
     steps, window = 0, 0
     while steps < args.total_steps:
         if args.redraw and window and window % args.redraw == 0:
-            plan = env.league_plan(draw_lineup(A, K, N, args.with_replacement, g).to(env.device), A)
+            plan = draw()
         rec = video.start(window) if video else None
         out = env.league_window(params, state, T, plan, info=True)
         if rec is not None:

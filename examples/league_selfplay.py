@@ -6,7 +6,8 @@ columns its line-up put it in, however many, in three launches (include/wurm_hip
     per window:  league_window -> pop.update(state, out, plan=plan, learn=...) -> LeagueTable.update
 
 Every `--redraw` windows the line-ups are drawn again (`league_plan`: the only call of the loop that has to synchronise;
-the progress line every 50 windows reads the losses back) and, with
+the progress line every 50 windows reads the losses back; with `--device-draw` the line-ups are drawn and sorted on the
+device by `league_draw`, and the loop queues without a host read) and, with
 `--exploit`, population-based training takes its step on the scores of the windows since the last draw,
 `reward / steps` out of `LeagueTable.table` on the device: the worst policies become perturbed copies of the best.
 `--learners L` trains only the first L policies; the others stay as they are, a pool of frozen checkpoints the learners
@@ -15,6 +16,13 @@ meet (they still play and are still scored).  `step` is shared by the policies (
     python examples/league_selfplay.py --n-policies 8 --n-agents 4 --num-envs 512 --total-steps 2000000
     python examples/league_selfplay.py --n-policies 16 --learners 4 --params pool.pt --redraw 50
     python examples/league_selfplay.py --n-policies 4 --n-agents 2 --num-envs 8 --size 12 --total-steps 1600 --exploit
+    python examples/league_selfplay.py --n-policies 8 --device-draw --matchmaking prioritised --redraw 5
+    python examples/league_selfplay.py --n-policies 16 --learners 4 --device-draw --pin-learners
+
+`--device-draw` draws with `MultiSnake.league_draw`.  `--matchmaking prioritised` (with it) meets strong opponents more
+often: at every redraw the policies are ranked by reward per row-step out of `LeagueTable.table`, with torch ops on the
+device, and the policy of rank r (0 = best) holds A - r tickets; `uniform` gives every policy one.  `--pin-learners` (with
+it) seats the first L policies as snake 0 in turn, one per draw, and draws the other seats from the pool.
 
 `--params FILE` as for examples/league_eval.py; `--save FILE` writes `pop.state_dict()` at the end.
 """
@@ -45,6 +53,11 @@ def main(argv=None):
     ap.add_argument('--window-steps', type=int, default=20)
     ap.add_argument('--total-steps', type=int, default=2000000, help='env steps summed over the batch')
     ap.add_argument('--redraw', type=int, default=25, metavar='K', help='new line-ups every K windows')
+    ap.add_argument('--device-draw', action='store_true', help='draw and sort the line-ups on the device (league_draw)')
+    ap.add_argument('--matchmaking', choices=('uniform', 'prioritised'), default='uniform',
+                    help='prioritised (needs --device-draw): tickets by rank of reward per step in the table')
+    ap.add_argument('--pin-learners', action='store_true',
+                    help='(needs --device-draw) the first L policies take seat 0 in turn, the rest are drawn')
     ap.add_argument('--exploit', action='store_true', help='a PBT step (FusedA2CPopulation.exploit) at every redraw')
     ap.add_argument('--lr', type=float, default=1e-3)
     ap.add_argument('--gamma', type=float, default=0.99)
@@ -62,6 +75,8 @@ def main(argv=None):
         raise SystemExit(f'--learners must lie in [1, {A}]')
     if args.exploit and L < A:
         raise SystemExit('--exploit replaces the worst policies, frozen ones included: use it without --learners')
+    if (args.matchmaking != 'uniform' or args.pin_learners) and not args.device_draw:
+        raise SystemExit('--matchmaking prioritised and --pin-learners draw on the device: add --device-draw')
     torch.manual_seed(args.seed)
     env = MultiSnake(num_envs=N, num_snakes=K, size=args.size, observation_mode=args.observation, device=args.device,
                      boost=False, food_mode='random_rate', respawn_mode='any', seed=args.seed)
@@ -75,16 +90,34 @@ def main(argv=None):
     learn = None if L == A else (torch.arange(A, device=env.device) < L)   # a device mask, made once
     table = LeagueTable(A, env.device)
     g = torch.Generator().manual_seed(args.seed)
-    draw = lambda: env.league_plan(draw_lineup(A, K, N, args.with_replacement, g).to(env.device), A)
-    plan = draw()
+
+    def tickets():
+        """None (one ticket each), or A - rank by reward per row-step since the last draw: torch ops on the device, no
+        host read.  A policy that did not play (0 / 0 = NaN) ranks last; before the first window all do, in index order."""
+        if args.matchmaking == 'uniform':
+            return None
+        score = torch.nan_to_num(table.table[:, 1] / table.table[:, 0], nan=float('-inf'))
+        best_first = torch.argsort(score, descending=True, stable=True)
+        held = torch.empty(A, dtype=torch.int32, device=env.device)
+        held[best_first] = torch.arange(A, 0, -1, dtype=torch.int32, device=env.device)
+        return held
+
+    def draw(held=None):
+        if not args.device_draw:
+            return env.league_plan(draw_lineup(A, K, N, args.with_replacement, g).to(env.device), A)
+        pinned = [env.league_draws % L] + [-1] * (K - 1) if args.pin_learners else None
+        return env.league_draw(A, tickets=held, replacement=args.with_replacement, pinned=pinned)
+
+    plan = draw(tickets())
     state = env.reset()
     steps, window = 0, 0
     while steps < args.total_steps:
         if window and window % args.redraw == 0:
+            held = tickets()   # (from the table as it stands, before --exploit clears it)
             if args.exploit:   # reward per row-step since the last draw; a policy that did not play (0 / 0 = NaN) is worst
                 pop.exploit(table.table[:, 1] / table.table[:, 0], seed=args.seed)
                 table.reset()
-            plan = draw()
+            plan = draw(held)
         out = env.league_window(pop.params, state, T, plan, info=True)
         res = pop.update(state, out, plan=plan, learn=learn)
         table.update(plan, out)

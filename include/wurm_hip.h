@@ -645,6 +645,78 @@ int wurm_multi_league_scores(const float *rewards, const uint8_t *dones, const f
                              const int32_t *order, const int64_t *offsets, double *table, int64_t num_rows,
                              int64_t num_steps, int num_policies, void *stream);
 
+/* Matchmaking on the device: the line-up of such a league DRAWN from integer tickets, and the order / offsets lists of any
+ * line-up BUILT, both without a host read (kernels: wurm_amd/csrc/multi_matchmaking.hpp).  Each of the two calls takes ONE
+ * argument block whose last member is the stream, the calling style of wurm_single_call / wurm_multi_call for calls of
+ * many arguments.  The prototypes therefore have no `stream` parameter: the table of stream cases (tests/stream_cases.py,
+ * which tests/test_stream_inventory.py holds against the prototypes that have one) does not list them, and their stream
+ * cases are in tests/test_league_draw_gpu.py; a later change may move them into the table.
+ *
+ * wurm_league_draw.  Per env i (global id env_offset + i), seats k = 0 .. num_snakes - 1 in order:
+ *   a seat with pinned[k] >= 0 goes to that policy, without a draw;
+ *   else the pool is every policy — with replacement = 0 less the pinned ones (all of them, before any seat is drawn) and
+ *   those already seated in this env;  t[a] = max(tickets[a], 0) (1 with tickets = NULL), total = the sum of t over the
+ *   pool;  if total = 0 every member of the pool counts 1 and total = the size of the pool;
+ *   w = Philox(seed; env = env_offset + i, call, purpose 10, sub = k);  x = w[0] << 32 | w[1];
+ *   r = the high 64 bits of x * total;  the seat goes to the smallest a of the pool whose running sum of t, over the pool
+ *   in ascending order, exceeds r.
+ * Exact integer arithmetic: an env's seats depend on seed, call, env_offset + i, the tickets and the arguments, not on
+ * num_envs nor on another env.  `call` is a counter of LINE-UP draws the caller keeps beside the env's own and the policy
+ * call counter; this entry point consumes neither of those.
+ *   tickets (num_policies) int32, device, nullable;  lineup (num_snakes, num_envs) int64, device, written
+ *   pinned  HOST pointer to num_snakes ints, nullable (= all -1); read during the call only
+ * Refused before any HIP call: a null block; negative num_envs or env_offset, num_snakes < 1, num_policies < 1, a pinned
+ * entry outside [-1, num_policies), with replacement = 0 num_policies < num_snakes or a policy pinned twice, and — with
+ * num_envs > 0 — a null lineup (WURM_ERR_INVALID_ARG); num_snakes > 64, num_snakes * num_envs >= 2^31 and env_offset +
+ * num_envs > 2^32 (WURM_ERR_UNSUPPORTED).  num_envs = 0 is a successful no-op without a launch.  Otherwise exactly ONE
+ * launch on `stream`, one env per lane; no atomics, no scratch. */
+typedef struct wurm_league_draw {
+    const int32_t *tickets;
+    int64_t *lineup;
+    const int32_t *pinned;
+    int64_t num_envs, env_offset;
+    uint64_t seed, call;
+    int num_snakes, num_policies, replacement;
+    void *stream;
+} wurm_league_draw;
+int wurm_multi_league_draw(const wurm_league_draw *args);
+
+/* wurm_league_plan: what MultiSnake.league_plan computes with torch ops, bit for bit, in WURM_LEAGUE_PLAN_LAUNCHES launches.
+ *   lineup  (num_rows) integers of lineup_dtype, device: entry r = k * num_envs + i names the policy of row r
+ *   order   (num_rows) int32, written: the rows with an entry in [0, num_policies) sorted by policy, ascending within a
+ *           policy (a stable counting sort); the entries behind offsets[num_policies] are set to -1
+ *   offsets (num_policies + 1) int64, written: the cumulative counts
+ *   dropped int32 scalar, written: the number of rows whose entry lies outside [0, num_policies); they are in no list
+ *   workspace: wurm_multi_league_plan_workspace_bytes(num_rows, num_policies) bytes, 8-byte aligned, contents ignored.
+ *           Sized from the two numbers alone (a (chunks, num_policies) int32 table of counts, at most 256 chunks, and a
+ *           sum per 256 policies); 0 from the query = refused sizes.  Any num_policies: above 256, above num_rows.
+ * The launches: counts per (chunk of rows, policy) — integer atomic adds, whose sum does not depend on their order —, a
+ * scan over the chunks per policy, a scan over the policies, and the placement of every row by ballot within its wave,
+ * the waves of a chunk in order.  No grid-wide barrier, no floating point: the same bits every run.
+ * Refused before any HIP call: a null block; negative num_rows, num_policies < 1, a lineup_dtype that is none of the five
+ * below and — with num_rows > 0 — null lineup, order, offsets, dropped or workspace, a workspace that is too small or not
+ * 8-byte aligned (WURM_ERR_INVALID_ARG); num_rows >= 2^31 (WURM_ERR_UNSUPPORTED).  num_rows = 0 is a successful no-op
+ * without a launch (the caller zeroes offsets and dropped).  Otherwise exactly WURM_LEAGUE_PLAN_LAUNCHES launches on
+ * `stream`, their grids sized from num_rows and num_policies alone. */
+#define WURM_LEAGUE_PLAN_LAUNCHES 4
+#define WURM_LINEUP_I64 0
+#define WURM_LINEUP_I32 1
+#define WURM_LINEUP_I16 2
+#define WURM_LINEUP_I8 3
+#define WURM_LINEUP_U8 4
+typedef struct wurm_league_plan {
+    const void *lineup;
+    int32_t *order;
+    int64_t *offsets;
+    int32_t *dropped;
+    void *workspace;
+    int64_t workspace_bytes, num_rows;
+    int num_policies, lineup_dtype;
+    void *stream;
+} wurm_league_plan;
+int64_t wurm_multi_league_plan_workspace_bytes(int64_t num_rows, int num_policies);
+int wurm_multi_league_plan(const wurm_league_plan *args);
+
 /* wurm.utils.determine_orientations (wurm/utils.py:36-65) over a (n,3,S,S) batch; out (n) int64. */
 int wurm_orientations(const float *envs, int64_t *out, int64_t n, int size, void *stream);
 

@@ -42,6 +42,7 @@ SYMBOLS = [
     'wurm_multi_rollout_frames',
     'wurm_multi_policy_window_plan', 'wurm_multi_policy_window',
     'wurm_multi_act_league', 'wurm_multi_league_scores',
+    'wurm_multi_league_draw', 'wurm_multi_league_plan_workspace_bytes', 'wurm_multi_league_plan',
     'wurm_a2c_ff_league_workspace_bytes', 'wurm_a2c_ff_league_grad', 'wurm_a2c_ff_league_grad_gae',
     'wurm_a2c_ff_league_apply', 'wurm_a2c_ff_league_update', 'wurm_a2c_ff_league_update_gae',
 ]
@@ -117,6 +118,26 @@ class MultiPolicyWindowCall(ctypes.Structure):
         ('pre_call', ctypes.c_uint64), ('policy_call0', ctypes.c_uint64), ('num_snakes', ctypes.c_int),
         ('size', ctypes.c_int), ('obs_n', ctypes.c_int), ('num_species', ctypes.c_int),
         ('waves_per_group', ctypes.c_int), ('cfg', MultiConfig)]
+
+
+class LeagueDraw(ctypes.Structure):
+    """wurm_league_draw of include/wurm_hip.h (`pinned` is a HOST pointer)"""
+    _fields_ = [('tickets', ctypes.c_void_p), ('lineup', ctypes.c_void_p), ('pinned', ctypes.c_void_p),
+                ('num_envs', ctypes.c_int64), ('env_offset', ctypes.c_int64), ('seed', ctypes.c_uint64),
+                ('call', ctypes.c_uint64), ('num_snakes', ctypes.c_int), ('num_policies', ctypes.c_int),
+                ('replacement', ctypes.c_int), ('stream', ctypes.c_void_p)]
+
+
+class LeaguePlanCall(ctypes.Structure):
+    """wurm_league_plan of include/wurm_hip.h"""
+    _fields_ = [('lineup', ctypes.c_void_p), ('order', ctypes.c_void_p), ('offsets', ctypes.c_void_p),
+                ('dropped', ctypes.c_void_p), ('workspace', ctypes.c_void_p), ('workspace_bytes', ctypes.c_int64),
+                ('num_rows', ctypes.c_int64), ('num_policies', ctypes.c_int), ('lineup_dtype', ctypes.c_int),
+                ('stream', ctypes.c_void_p)]
+
+
+LINEUP_I64, LINEUP_I32, LINEUP_I16, LINEUP_I8, LINEUP_U8 = range(5)
+LEAGUE_PLAN_LAUNCHES = 4   # WURM_LEAGUE_PLAN_LAUNCHES of include/wurm_hip.h
 
 
 def multi_config(num_snakes, boost, food_on_death_prob, boost_cost_prob, food_mode, food_rate, reward_on_death,

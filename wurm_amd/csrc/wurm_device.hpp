@@ -18,8 +18,9 @@ typedef unsigned int u32;
 
 constexpr int WAVE = 64;
 
-// RNG purposes: one Philox stream per (env, call, purpose, sub-block).  0 - 8 must match oracle/oracle_common.h; 9 is
-// library-only (the oracle never draws it): env = member, call = generation (a2c_pbt.hpp).
+// RNG purposes: one Philox stream per (env, call, purpose, sub-block).  0 - 8 must match oracle/oracle_common.h; 9 and 10
+// are library-only (the oracle never draws them): 9 with env = member, call = generation (a2c_pbt.hpp), 10 with env =
+// env_offset + i, call = the env's line-up draw counter, sub = the seat (multi_matchmaking.hpp).
 enum : u32 {
     RNG_FOOD = 0,
     RNG_RESET = 1,
@@ -30,7 +31,8 @@ enum : u32 {
     RNG_SPAWN = 6,
     RNG_COLOUR = 7,
     RNG_POLICY = 8,
-    RNG_PBT = 9
+    RNG_PBT = 9,
+    RNG_LEAGUE = 10
 };
 
 struct Words {

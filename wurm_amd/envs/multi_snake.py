@@ -264,6 +264,10 @@ class MultiSnake(object):
         # the POLICY call counter: one per `act`, beside the env's own RNG counter (`_fs.call`), which `act` leaves alone.  A
         # plain attribute: a copy / pickle carries it as it carries `_copy_call`.
         self.policy_calls = 0
+        # the LINE-UP draw counter: one per `league_draw`, a third counter beside those two and carried the same way;
+        # `league_dropped`: the rows the last plan built on the device left out (wurm_amd/envs/_multi_league.py)
+        self.league_draws = 0
+        self.league_dropped = torch.zeros((), dtype=torch.int32, device=self.device)
 
         if render_args is None:
             self.render_args = {'num_rows': 1, 'num_cols': 1, 'size': 256}
@@ -372,6 +376,8 @@ class MultiSnake(object):
         st = dict(st)
         call, rewards, boost = st.pop('_copy_call'), st.pop('_copy_rewards'), st.pop('_copy_boost')
         self.__dict__.update(st)
+        self.__dict__.setdefault('league_draws', 0)        # (a state saved before the league drew on the device)
+        self.__dict__.setdefault('league_dropped', None)
         self._make_machine()
         self._fs.call = call
         self._fs.lazy_ok = self._lazy_ok()
@@ -910,16 +916,38 @@ class MultiSnake(object):
     # ------------------------------------------------------------------ a league: a line-up per env (extension;
     # wurm_amd/envs/_multi_league.py)
 
-    def league_plan(self, lineup: torch.Tensor, num_policies: int):
+    def league_plan(self, lineup: torch.Tensor, num_policies: int, sync: bool = True):
         """The row lists `act_league` / `league_window` / `wurm_amd.rl.LeagueTable.update` run on, once per draw of
         matchups.  lineup: (num_snakes, num_envs) integer tensor, `lineup[k, i]` the row of `params` that plays snake k of
         env i, each in [0, num_policies) — any policy any number of times, also twice in one env, also never.  Returns a
         `LeaguePlan(lineup, order, offsets, num_policies)`: `order` (K N) int32, the rows k * N + i sorted by policy (stable:
         ascending within a policy), `offsets` (num_policies + 1) int64 — torch ops on `lineup`'s device (a CPU line-up
         gives a CPU plan, which no launch takes).  One host synchronisation, the range check; RuntimeError for a wrong
-        shape or dtype and for an entry outside [0, num_policies)."""
+        shape or dtype and for an entry outside [0, num_policies).
+        sync=False: the same two lists, bit for bit, by HIP kernels on the current stream (include/wurm_hip.h:
+        wurm_multi_league_plan, WURM_LEAGUE_PLAN_LAUNCHES launches) and no host read — usable inside a queued sequence.  The
+        line-up must be contiguous and on the env's device.  An entry outside [0, num_policies) cannot be refused then:
+        its row is left out of every list and counted in `league_dropped` (a device int32 scalar, rewritten by every
+        such call); `order` keeps its length and holds -1 behind `offsets[num_policies]`, which no consumer reads."""
         from wurm_amd.envs import _multi_league
-        return _multi_league.league_plan(self, lineup, num_policies)
+        return _multi_league.league_plan(self, lineup, num_policies, sync)
+
+    def league_draw(self, num_policies: int, tickets: torch.Tensor = None, replacement: bool = False, pinned=None):
+        """Draws a line-up per env ON THE DEVICE and returns its `LeaguePlan` (`plan.lineup` (K, N) int64): one launch for
+        the draw, then the launches of `league_plan(..., sync=False)`, no host read.  Per env, seats k = 0 .. K - 1 in
+        order: policy a is drawn with probability proportional to max(tickets[a], 0) among the policies in the pool.
+        tickets: (num_policies,) int32 on the env's device, None = one each; integers, so that the draw is exact
+            arithmetic (turn scores into tickets with torch ops on the device).  A pool whose tickets are all 0 is
+            drawn from uniformly.
+        replacement=False: no policy sits twice in one env (num_policies >= num_snakes).
+        pinned: K ints or None; pinned[k] >= 0 seats that policy as snake k in every env, -1 leaves the seat to the
+            draw.  Without replacement every pinned policy leaves the pool before any seat is drawn.
+        Env i's seats depend on `seed`, `league_draws`, env_offset + i, the tickets and the arguments only: a shard draws
+        its rows of the whole batch.  `league_draws` grows by one; the env's own counter, `policy_calls`, its state and
+        a postponed reset are left alone.  RuntimeError, before anything is launched, for arguments of the wrong type,
+        shape, dtype, device or range."""
+        from wurm_amd.envs import _multi_league
+        return _multi_league.league_draw(self, num_policies, tickets, replacement, pinned)
 
     def act_league(self, params: torch.Tensor, observations, plan) -> dict:
         """`act` with the policy of every (snake, env) row taken from `plan` (the reference's experiments/eval.py plays
